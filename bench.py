@@ -14,10 +14,12 @@ against the replicated 100k-entry gallery (so every rank holds the whole batch's
 By default TWO batches are in flight per GPU (--streams 2): steps are issued round-robin to two independent
 library contexts on separate HIP streams, so the latency-bound kernels of one batch (IResNet at 64 faces has
 only 100-400 tiles per layer) overlap the other batch's.  Every step is still one full pass over one batch and all
-K steps complete inside a timed region.  The K-step region (barrier + synchronize on both sides, MAX over ranks) is
-repeated --repeats times (default 5) and the MEDIAN repeat is reported; `ms_per_step_repeats` lists them all.
+K steps complete inside a timed region (barrier + synchronize on both sides, MAX over ranks).
 
-Prints ONE JSON line on rank 0 (contract in the task description), with
+A plain run sets up, warms up, times exactly K steps once, writes the last timed step's outputs when --dump-outputs DIR is
+given, and prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, config).
+--full adds what the headline figure does not need: the K-step region repeated --repeats times (default 5, the MEDIAN
+repeat reported; `ms_per_step_repeats` lists them all), the one-lane and rec_group-1 legs, and rank 0's checker legs:
   roofline:     all MFMA conv launches of one step (the dominant kernel family): algorithmic FLOPs (2 x MACs of the true
                 channel counts) and algorithmic HBM bytes (every op's input + residual + output + weights as stored)
                 over their summed device time (HIP events on the library's stream); BOTH floors are reported per net
@@ -27,6 +29,11 @@ Prints ONE JSON line on rank 0 (contract in the task description), with
   embed_cosine_delta_max / match_score_delta_max: device embeddings / gallery scores vs the oracle's on identical
                 landmarks (the second half of BASELINE.json's metric)
   faces_per_s_F8, ms_per_step_h2d_included: side legs (F in {1, 8}; H2D reported separately).
+
+--dump-outputs DIR writes what the last timed step handed its caller as DIR/<name>.npy (float32 / float64): that step's
+detections (bboxes, det_scores, landmarks, face_counts: the faces max_num keeps per frame), its raw and unit embeddings and its
+gallery matches (match_index, -1 = Unknown; match_score).  Frames, weights and gallery are seeded: the same arguments give the
+same inputs on every run, so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -287,12 +294,34 @@ def detector_agreement(pipe, frames, det_net, det_P, rec_net, rec_P, n_frames, n
             "head_err_note": f"max |device - fp32 oracle| over {n_frames} frames; score = sigmoid output (test bound 4e-3 at 640 x 640), bbox / kps in stride units (3e-2)"}
 
 
+def host_array(buf):
+    """a device buffer (torch tensor or the library's DeviceBuffer) as a numpy array"""
+    return buf.detach().cpu().numpy() if hasattr(buf, "detach") else buf.download()
+
+
+def dump_outputs(out_dir, arrays, budget=64 << 20):
+    """DIR/<name>.npy per array; above `budget` bytes in all, every array keeps a fixed, seeded sample of its rows"""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > budget and a.ndim and a.shape[0] > 1:
+            k = max(1, a.shape[0] * budget // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], k, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5, help="the K-step timed region is repeated this often; the median is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: repeated timed regions, the one-lane / rec_group-1 legs, roofline, "
+                         "oracle comparisons, side legs and the CPU baseline (a plain run times the K steps once and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (detections, embeddings, matches) as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the K-step timed region is repeated this often; the median is reported (default 1, 5 with --full)")
     ap.add_argument("--batch", type=int, default=64, help="frames per GPU per step")
     ap.add_argument("--faces-per-frame", type=int, default=1)
     ap.add_argument("--gallery", type=int, default=0, help="gallery entries (0 = 1000 at N = 1 [cfg 2], 100000 at N > 1 [cfg 3])")
@@ -318,6 +347,8 @@ def main():
                     help="pipelines in flight per GPU: steps are issued round-robin to this many independent "
                          "contexts/HIP streams so that the small kernels of one batch overlap another batch's")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     if "FID_PLAN" not in os.environ and "FID_PLAN_RO" not in os.environ and os.path.exists(DEFAULT_PLAN):
         os.environ["FID_PLAN_RO"] = DEFAULT_PLAN
@@ -440,7 +471,7 @@ def main():
                     ln.dist = StagedDist if args.backend == "gloo" else dist
         lanes.append(ln)
     pipe, frames_dev = lanes[0].pipe, lanes[0].frames_dev
-    if RG > 1:                                            # the checker legs (cosine delta, survivor agreement, roofline events) look at ONE batch: a plain pipeline on lane 0's nets
+    if RG > 1 and args.full:                              # the checker legs (cosine delta, survivor agreement, roofline events) look at ONE batch: a plain pipeline on lane 0's nets
         with torch.cuda.stream(lanes[0].stream):
             pipe = FacePipeline(ctx, det, rec, batch=B, faces_per_frame=F)
 
@@ -514,6 +545,39 @@ def main():
             el = float(t.item())
         return el
 
+    def last_step_outputs():
+        """What the last timed step (index steps - 1 of the last region) handed its caller, on this rank: its detections, raw and unit
+        embeddings and gallery matches (at N > 1 the gathered unit embeddings and, match scope 'all' / 'sharded', the matches of that step
+        on every rank).  Face slots past a frame's face count are zeroed in the rank's own arrays: a caller never receives them."""
+        i = args.steps - 1
+        if args.schedule == "stages" and world == 1:
+            ln, p, rec, steps = None, spipes[i & 1], recB, 1
+        else:
+            ln = lanes[i % len(lanes)]
+            p, rec = ln.pipe, ln.rec
+            steps = p.last_steps if RG > 1 else 1                         # the lane's last group ends with its last step
+        j, n = steps - 1, p.n_slots
+        post = p.posts[j] if RG > 1 else p.post
+        post.check()
+        counts = np.minimum(post.counts.download()[:B], F)
+        keep = (np.arange(F)[None, :] < counts[:, None]).astype(np.float32)             # [B, F]
+        det = post.det.download()[:B, :F] * keep[..., None]
+        kps = post.kps.download()[:B, :F] * keep[..., None]
+        emb = rec.read(rec.low.outputs[0], steps * n).reshape(steps * n, -1)[j * n:(j + 1) * n] * keep.reshape(n, 1)
+        own = slice(j * n, (j + 1) * n)
+        if world == 1:
+            q, idx, score = host_array(p.q)[own], host_array(p.idx)[own], host_array(p.score)[own]
+        else:
+            rows = np.concatenate([np.arange(r * steps * n + j * n, r * steps * n + (j + 1) * n) for r in range(world)])
+            q = host_array(ln.q_all)[rows]
+            if args.match_scope == "own":
+                idx, score = host_array(p.idx)[own], host_array(p.score)[own]
+            else:
+                idx, score = host_array(ln.idx_all)[rows], host_array(ln.score_all)[rows]
+        return {"bboxes": det[..., :4], "det_scores": det[..., 4], "landmarks": kps.reshape(B, F, 5, 2),
+                "face_counts": counts.astype(np.float32), "embeddings": emb.reshape(B, F, -1).astype(np.float32),
+                "unit_embeddings": q.astype(np.float32), "match_index": idx.astype(np.float64), "match_score": score.astype(np.float32)}
+
     # what the plan file really installed (VERDICT r3 item 5): its picks are keyed by ISA name + CU count + layer-table hash + candidate-set
     # revision, so a file that does not match this box / library installs NOTHING and every op is tuned at start-up instead -- the line says so
     plan_path = os.environ.get("FID_PLAN") or os.environ.get("FID_PLAN_RO")
@@ -531,7 +595,7 @@ def main():
                     step(li)
                 step(li, flush=True)
                 torch.cuda.synchronize()
-        if world == 1:
+        if world == 1 and args.full:
             pipe.run_step(frames_dev, 640, 640, gallery, thresh)                   # (the checker pipeline's recogniser batch)
             torch.cuda.synchronize()
     post_picks = {"det": picks_at(det, B), "rec": picks_at(rec, B * F * RG)}
@@ -547,9 +611,12 @@ def main():
     elapsed = float(np.median(repeats))
     host_enqueue_ms = float(np.median(enqueue_s)) * 1e3
     log(f"timed regions done: {[round(r / args.steps * 1e3, 3) for r in repeats]} ms/step, median {elapsed / args.steps * 1e3:.3f}")
+    if args.dump_outputs and rank == 0:                  # before any other leg reuses the buffers
+        dump_outputs(args.dump_outputs, last_step_outputs())
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
     # the same steps on ONE lane (VERDICT r3 item 5 / Weak 9): a kernel change that is slower alone but faster in the two-lane step stays visible
     one_lane_ms = None
-    if len(lanes) > 1 and not args.no_one_lane:
+    if args.full and len(lanes) > 1 and not args.no_one_lane:
         def step_lane0(i):
             step(0)
         one = [timed_region(step_lane0, args.steps) for _ in range(3)]
@@ -557,7 +624,7 @@ def main():
         log(f"one lane: {[round(r / args.steps * 1e3, 3) for r in one]} ms/step")
     # ... and the same lanes with the recogniser run per step (rec_group 1): what the grouping buys stays on the line
     ungrouped_ms = None
-    if RG > 1 and world == 1 and not args.no_one_lane:
+    if args.full and RG > 1 and world == 1 and not args.no_one_lane:
         for ln in lanes:
             with torch.cuda.stream(ln.stream):
                 ln.pipe1 = FacePipeline(ln.ctx, ln.det, ln.rec, batch=B, faces_per_frame=F)
@@ -620,10 +687,10 @@ def main():
             out["ms_per_step_1lane"] = round(one_lane_ms, 4)
         if ungrouped_ms is not None:
             out["ms_per_step_rec_group1"] = round(ungrouped_ms, 4)
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             log("roofline: per-op HIP-event timing")
             out["roofline"] = mfma_roofline(pipe, frames_dev, B, F, RG, crops=lanes[0].pipe.crops)
-    side = rank == 0 and world == 1 and args.cpu_frames > 0
+    side = args.full and rank == 0 and world == 1 and args.cpu_frames > 0
     if side:
         # the batch the roofline leg left in the pipeline is `frames`; re-run one step so idx/score/kps belong to it
         pipe.run_step(frames_dev, 640, 640, gallery, thresh)

@@ -5,7 +5,7 @@ A="$1"; B="$2"; R="${3:-3}"
 for i in $(seq $R); do
   for v in A B; do
     if [ $v = A ]; then E="$A"; else E="$B"; fi
-    ms=$(env $E python bench.py --steps 40 --warmup 5 --cpu-frames 0 --no-roofline | python -c "import json,sys; print(json.loads(sys.stdin.readline())['ms_per_step'])") || exit 1
+    ms=$(env $E python bench.py --full --steps 40 --warmup 5 --cpu-frames 0 --no-roofline | python -c "import json,sys; print(json.loads(sys.stdin.readline())['ms_per_step'])") || exit 1
     echo "$v [$E] $ms"
   done
 done

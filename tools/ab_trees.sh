@@ -5,4 +5,4 @@ R=$GRAFT_REPO_ROOT
 n=$1; t=$2
 (cd $R/tmp_ab/$t/scrfd_arcface_facerecognition_amd/csrc && make -j16 > /tmp/build_$t.log 2>&1) || { echo "build $t failed"; tail -3 /tmp/build_$t.log; exit 1; }
 one() { (cd $1 && python bench.py --steps 40 --warmup 5 --cpu-frames 0 --no-roofline $3 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readline()); print('$2', d['ms_per_step'], d.get('ms_per_step_1lane'))"); }
-for i in $(seq $n); do one $R/tmp_ab/$t $t; one $R work; done
+for i in $(seq $n); do one $R/tmp_ab/$t $t; one $R work --full; done

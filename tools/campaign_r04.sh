@@ -9,7 +9,7 @@ mkdir -p $O
 part=${1:-a}
 export FID_PLAN_RO=$R/plans/mi355x.plan
 if [ "$part" = a ]; then
-  python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
+  python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
   tail -c 600 $O/bench_default.json
   bash $R/tools/collect_profiles.sh r04 > $O/collect.log 2>&1
   P=$R/gpurun_out/prof_r04

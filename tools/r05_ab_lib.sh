@@ -10,7 +10,7 @@ meas() {
     set -- $spec
     FID_LIB_DIR=$L python3 tools/run_r50_steady.py $1 $2 30 2>&1 | tail -1 | sed "s/^/$T /"
   done
-  python3 bench.py --steps 40 --warmup 6 --cpu-frames 0 --no-roofline 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.readline()); print('$T bench ms_per_step', d['ms_per_step'], 'one lane', d.get('ms_per_step_1lane'))"
+  python3 bench.py --full --steps 40 --warmup 6 --cpu-frames 0 --no-roofline 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.readline()); print('$T bench ms_per_step', d['ms_per_step'], 'one lane', d.get('ms_per_step_1lane'))"
 }
 cp scrfd_arcface_facerecognition_amd/libfaceid.so /tmp/libfaceid.work.so
 for i in $(seq $n); do

@@ -9,7 +9,7 @@ cp scrfd_arcface_facerecognition_amd/libfaceid.so /tmp/libfaceid.work.so
 for i in $(seq $n); do
   for T in $t work; do
     if [ $T = work ]; then cp /tmp/libfaceid.work.so scrfd_arcface_facerecognition_amd/libfaceid.so; else cp tmp_ab/$t/scrfd_arcface_facerecognition_amd/libfaceid.so scrfd_arcface_facerecognition_amd/libfaceid.so; fi
-    python3 bench.py --steps 40 --warmup 6 --cpu-frames 0 --no-roofline 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.readline()); print('$T bench ms_per_step', d['ms_per_step'], 'one lane', d.get('ms_per_step_1lane'), 'rg1', d.get('ms_per_step_rec_group1'))"
+    python3 bench.py --full --steps 40 --warmup 6 --cpu-frames 0 --no-roofline 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.readline()); print('$T bench ms_per_step', d['ms_per_step'], 'one lane', d.get('ms_per_step_1lane'), 'rg1', d.get('ms_per_step_rec_group1'))"
   done
 done | tee -a $O/ab_lib_bench_$t.txt
 cp /tmp/libfaceid.work.so scrfd_arcface_facerecognition_amd/libfaceid.so
