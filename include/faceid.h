@@ -170,6 +170,24 @@ int fid_align_crops(fid_ctx *ctx, const uint8_t *frames_dev, int B, int H, int W
                     const float *kps_dev, const int32_t *counts_dev, int cap, int faces_per_frame,
                     uint8_t *crops_dev, double *M_dev);
 
+/* ---- packed face lists: every detected face of a batch as ONE dense row table, no per-frame padding.  The reference embeds every
+ * face detect() returns (main.py:130-134: `detect(frame, params.max_num)` then `recognizer(frame, kps)` per face) and its default
+ * max_num = 0 returns every NMS survivor (models/scrfd.py:159-177 selects only when max_num > 0); a B x faces_per_frame slot grid
+ * pays for its most crowded frame in every frame.
+ * fid_face_pack: k_b = min(max(counts[b], 0), cap) and, when max_per_frame > 0, also min(., max_per_frame).  offsets [B+1] = exclusive
+ * prefix sum of k_b; offsets[B] = total faces, NOT clipped to row_cap (overflow is visible after the fact, as with fid_scrfd_check).
+ * src [row_cap]: src[i] = b * cap + f -- the index of the i-th face, in (frame, rank) order, in det [B,cap,5] / kps [B,cap,10] of
+ * fid_scrfd_postprocess -- for i < min(total, row_cap), -1 for the rows after them.  Faces beyond row_cap (the last ones in that
+ * order) are dropped.  One launch; B * cap must fit an int32. */
+int fid_face_pack(fid_ctx *ctx, const int32_t *counts_dev, int B, int cap, int max_per_frame,
+                  int32_t *offsets_dev, int32_t *src_dev, int row_cap);
+/* fid_align_crops driven by the row table (one recogniser input per face of main.py:130-134, all of models/scrfd.py:159-177's
+ * survivors; the warp itself is utils/helpers.py:18-59): row i < n_rows with src[i] = b*cap+f >= 0
+ * gets exactly the crop (and M row) fid_align_crops writes for face f of frame b; src[i] < 0 -> zero crop, zero M.
+ * crops: uint8 [n_rows,112,112,3]; M_dev (optional, may be NULL): [n_rows, 6].  n_rows <= 65535. */
+int fid_align_crops_packed(fid_ctx *ctx, const uint8_t *frames_dev, int B, int H, int W, const float *kps_dev, int cap,
+                           const int32_t *src_dev, int n_rows, uint8_t *crops_dev, double *M_dev);
+
 /* ---- face gates of the reference's product layer: replaces smart_face_recognition.py:1145-1216
  * (assess_face_quality), :1218-1297 (get_face_pose_angles / is_side_face), :1299-1399 (analyze_bbox_for_side_face) and the
  * best-face selection with its four rejections (:1473-1519), for every face of a batch in one launch on the post-process's own
@@ -208,6 +226,11 @@ int fid_l2_normalize_f16(fid_ctx *ctx, const float *emb_dev, int n, int dim, voi
  * empty slots (row == {-0.0, +0.0 ...} <=> no face; pipeline.gathered_face_counts). */
 int fid_l2_normalize_f16_slots(fid_ctx *ctx, const float *emb_dev, int n, int dim, const int32_t *counts_dev,
                                int faces_per_frame, void *out_f16_dev);
+
+/* the same for the rows of a packed table (fid_face_pack; main.py:130-134, models/scrfd.py:159-177): src[i] < 0 -> the empty-slot marker
+ * row (-0.0 then +0.0s); otherwise the arithmetic of fid_l2_normalize_f16 (degenerate embedding -> all +0.0 row). */
+int fid_l2_normalize_f16_packed(fid_ctx *ctx, const float *emb_dev, int n_rows, int dim, const int32_t *src_dev,
+                                void *out_f16_dev);
 
 /* ---- gallery match: replaces the per-target python loop of reference main.py:136-142 --------
  * gallery: host fp32 [G, dim] raw embeddings (as build_targets collects them, main.py:102-103).

@@ -89,6 +89,55 @@ class FaceAnalysis:
                      normed_embedding=normed[i].copy(), quality={k: float(quality[0, i, j]) for j, k in enumerate(QUALITY_KEYS)},
                      is_side_face=bool(side_flag[0, i]), side_face_score=int(side_score[0, i])) for i in range(n)]
 
+    def get_batch(self, images, max_num: int = 0) -> List[List[Face]]:
+        """get() for a batch of images of ONE shape ([B,H,W,3] or a list): the detector runs on the batch (`SCRFD.detect_batch`, in its
+        chunks of `max_batch` images), and all faces of a chunk's images -- every one, the reference's max_num = 0 default, or its
+        top-`max_num` per image -- go through alignment, recogniser and normalisation as one packed row list (fid_face_pack), in runs of
+        at most `max_faces` rows: nothing is truncated.  Gates: `face_gates` on the chunk's detections.  -> per image its list of Face."""
+        images = np.ascontiguousarray(np.stack([np.asarray(im, dtype=np.uint8) for im in images]) if isinstance(images, (list, tuple)) else images,
+                                      dtype=np.uint8)
+        assert images.ndim == 4 and images.shape[3] == 3, images.shape
+        ctx, lib = self.ctx, self.ctx.lib
+        H, W = images.shape[1:3]
+        net = self.rec.session.compiled()
+        out: List[List[Face]] = []
+        step = self.det._max_batch
+        for b0 in range(0, images.shape[0], step):
+            chunk = images[b0:b0 + step]
+            B = chunk.shape[0]
+            dets = self.det._detect_chunk(chunk, max_num, "max")        # host results; the post-process's device arrays stay valid
+            post = self.det._postprocessor()
+            total = sum(len(d) for d, _ in dets)
+            if total == 0:
+                out += [[] for _ in range(B)]
+                continue
+            fr = ctx.to_device(chunk)
+            offsets, src = ctx.empty((B + 1,), np.int32), ctx.empty((total,), np.int32)
+            check(lib.fid_face_pack(ctx.handle, C.c_void_p(post.counts.ptr), B, post.cap, 0, C.c_void_p(offsets.ptr), C.c_void_p(src.ptr), total))
+            emb = np.empty((total, 512), np.float32)
+            normed = np.empty((total, 512), np.float32)
+            rows = min(total, self.max_faces)
+            crops, q = ctx.empty((rows, 112, 112, 3), np.uint8), ctx.empty((rows, 512), np.float16)
+            for r0 in range(0, total, self.max_faces):
+                n = min(self.max_faces, total - r0)
+                src_n = C.c_void_p(src.ptr + 4 * r0)
+                check(lib.fid_align_crops_packed(ctx.handle, C.c_void_p(fr.ptr), B, H, W, C.c_void_p(post.kps.ptr), post.cap, src_n, n,
+                                                 C.c_void_p(crops.ptr), None))
+                net.run_device(crops, n)
+                emb_ptr, _, _ = net.tensor(net.low.outputs[0])
+                check(lib.fid_l2_normalize_f16_packed(ctx.handle, C.c_void_p(emb_ptr), n, 512, src_n, C.c_void_p(q.ptr)))
+                emb[r0:r0 + n] = net.read(net.low.outputs[0], n).reshape(n, 512)
+                normed[r0:r0 + n] = q.download()[:n].astype(np.float32)
+            F = max(len(d) for d, _ in dets)
+            quality, side_score, side_flag, _ = face_gates(ctx, post.det, post.kps, post.counts, B, post.cap, F, self.gate_config)
+            off = offsets.download()
+            for b, (det, kpss) in enumerate(dets):
+                r = int(off[b])
+                out.append([Face(bbox=det[i, :4].copy(), det_score=float(det[i, 4]), kps=kpss[i].copy(), embedding=emb[r + i].copy(),
+                                 normed_embedding=normed[r + i].copy(), quality={k: float(quality[b, i, j]) for j, k in enumerate(QUALITY_KEYS)},
+                                 is_side_face=bool(side_flag[b, i]), side_face_score=int(side_score[b, i])) for i in range(len(det))])
+        return out
+
     def best_face(self, image: np.ndarray) -> Optional[Face]:
         """The reference's enrolment gate (smart_face_recognition.py:1473-1519): the first highest-det_score face, rejected (None, with
         `last_verdict` naming the reason) when its score is below `confidence_threshold`, when it is a side face, or when its overall

@@ -27,19 +27,16 @@ __device__ __forceinline__ long long cv_round(double v) {
 constexpr int OUT = 112;
 constexpr int ROWS_PER_BLOCK = 16;
 
-__global__ void __launch_bounds__(256) align_warp(const uint8_t *frames, int H, int W, const float *kps, const int *counts,
-                                                  int cap, int F, uint8_t *crops, double *M_out) {
-    const int slot = blockIdx.y;  // b * F + f
-    const int b = slot / F, f = slot - b * F;
-    const int y0 = blockIdx.x * ROWS_PER_BLOCK;
-    uint8_t *dst = crops + (size_t)slot * OUT * OUT * 3;
-    const bool valid = f < counts[b] && f < cap;
+// One block's share (ROWS_PER_BLOCK output rows from y0) of one face's crop: thread 0 estimates the transform from the landmarks `lm`
+// (NULL = no face: zero crop, zero M), every thread warps.  `src` = the face's frame, `dst` = its crop, `mo` = its row of M_out (or NULL).
+// Shared by align_warp (face slots) and align_warp_packed (dense row table): the two produce the same bytes by construction.
+__device__ __forceinline__ void align_face_rows(const uint8_t *src, int H, int W, const float *lm, uint8_t *dst, double *mo, int y0) {
+    const bool valid = lm != nullptr;
     __shared__ double sm[6];  // inverse map m00 m01 m02 m10 m11 m12
     __shared__ int ok;
     if (threadIdx.x == 0) {
         ok = 0;
         if (valid) {
-            const float *lm = kps + ((size_t)b * cap + f) * 10;
             // c_template holds the float32 template values widened to double, like skimage sees them
             double sx[5], sy[5], dx[5], dy[5], msx = 0, msy = 0, mdx = 0, mdy = 0;
             for (int i = 0; i < 5; i++) {
@@ -57,8 +54,7 @@ __global__ void __launch_bounds__(256) align_warp(const uint8_t *frames, int H, 
             }
             const double M00 = a / var, M01 = -bb / var, M10 = bb / var, M11 = a / var;
             const double M02 = mdx - (M00 * msx + M01 * msy), M12 = mdy - (M10 * msx + M11 * msy);
-            if (M_out) {
-                double *mo = M_out + (size_t)slot * 6;
+            if (mo) {
                 mo[0] = M00; mo[1] = M01; mo[2] = M02; mo[3] = M10; mo[4] = M11; mo[5] = M12;
             }
             // cv2.warpAffine inverts M (no WARP_INVERSE_MAP flag)
@@ -69,13 +65,11 @@ __global__ void __launch_bounds__(256) align_warp(const uint8_t *frames, int H, 
             sm[0] = m00; sm[1] = m01; sm[2] = -m00 * M02 - m01 * M12;
             sm[3] = m10; sm[4] = m11; sm[5] = -m10 * M02 - m11 * M12;
             ok = isfinite(M00) && isfinite(M01) && isfinite(M02) && isfinite(M12);
-        } else if (M_out && y0 == 0) {
-            double *mo = M_out + (size_t)slot * 6;
+        } else if (mo && y0 == 0) {
             for (int i = 0; i < 6; i++) mo[i] = 0.0;
         }
     }
     __syncthreads();
-    const uint8_t *src = frames + (size_t)b * H * W * 3;
     for (int p = threadIdx.x; p < ROWS_PER_BLOCK * OUT; p += blockDim.x) {
         const int y = y0 + p / OUT, x = p % OUT;
         uint8_t *o = dst + ((size_t)y * OUT + x) * 3;
@@ -98,6 +92,27 @@ __global__ void __launch_bounds__(256) align_warp(const uint8_t *frames, int H, 
         if (y1in && x1in) { const uint8_t *q = src + ((size_t)(iy + 1) * W + ix + 1) * 3; acc[0] += w11 * q[0]; acc[1] += w11 * q[1]; acc[2] += w11 * q[2]; }
         o[0] = (uint8_t)(acc[0] >> 10); o[1] = (uint8_t)(acc[1] >> 10); o[2] = (uint8_t)(acc[2] >> 10);
     }
+}
+
+__global__ void __launch_bounds__(256) align_warp(const uint8_t *frames, int H, int W, const float *kps, const int *counts,
+                                                  int cap, int F, uint8_t *crops, double *M_out) {
+    const int slot = blockIdx.y;  // b * F + f
+    const int b = slot / F, f = slot - b * F;
+    const bool valid = f < counts[b] && f < cap;
+    align_face_rows(frames + (size_t)b * H * W * 3, H, W, valid ? kps + ((size_t)b * cap + f) * 10 : nullptr,
+                    crops + (size_t)slot * OUT * OUT * 3, M_out ? M_out + (size_t)slot * 6 : nullptr, blockIdx.x * ROWS_PER_BLOCK);
+}
+
+// The same for a dense row table (fid_face_pack): row i holds face src[i] = b * cap + f of the post-process's arrays, or -1 = no face
+// (reference main.py:130-134 embeds every face models/scrfd.py:159-177 returned; the table lists them without per-frame padding).
+__global__ void __launch_bounds__(256) align_warp_packed(const uint8_t *frames, int B, int H, int W, const float *kps, int cap,
+                                                         const int *src_rows, uint8_t *crops, double *M_out) {
+    const int row = blockIdx.y;
+    const int s = src_rows[row];
+    const bool valid = s >= 0 && s < B * cap;
+    const int b = valid ? s / cap : 0;
+    align_face_rows(frames + (size_t)b * H * W * 3, H, W, valid ? kps + (size_t)s * 10 : nullptr,
+                    crops + (size_t)row * OUT * OUT * 3, M_out ? M_out + (size_t)row * 6 : nullptr, blockIdx.x * ROWS_PER_BLOCK);
 }
 
 // cv2.resize INTER_LINEAR u8 + zero letterbox paste (scrfd.py:135-138).
@@ -209,6 +224,20 @@ int fid_align_crops(fid_ctx *ctx, const uint8_t *frames_dev, int B, int H, int W
     dim3 grid(OUT / ROWS_PER_BLOCK, B * faces_per_frame);
     hipLaunchKernelGGL(align_warp, grid, dim3(256), 0, ctx->stream, frames_dev, H, W, kps_dev, counts_dev, cap,
                        faces_per_frame, crops_dev, M_dev);
+    FID_HIP(hipGetLastError());
+    return FID_OK;
+}
+
+int fid_align_crops_packed(fid_ctx *ctx, const uint8_t *frames_dev, int B, int H, int W, const float *kps_dev, int cap,
+                           const int32_t *src_dev, int n_rows, uint8_t *crops_dev, double *M_dev) {
+    FID_REQUIRE(ctx && frames_dev && kps_dev && src_dev && crops_dev, "NULL argument");
+    FID_REQUIRE(B > 0 && H > 0 && W > 0 && cap > 0 && n_rows > 0, "bad sizes");
+    FID_REQUIRE((long long)B * cap <= 0x7FFFFFFFll, "B * cap = %lld overflows the row table's int32 entries", (long long)B * cap);
+    FID_REQUIRE(n_rows <= 65535, "too many face rows per call (%d)", n_rows);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
+    dim3 grid(OUT / ROWS_PER_BLOCK, n_rows);
+    hipLaunchKernelGGL(align_warp_packed, grid, dim3(256), 0, ctx->stream, frames_dev, B, H, W, kps_dev, cap, src_dev, crops_dev, M_dev);
     FID_HIP(hipGetLastError());
     return FID_OK;
 }

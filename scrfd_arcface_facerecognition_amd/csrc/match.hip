@@ -20,13 +20,15 @@ namespace {
 // counts != NULL: row = face slot (frame row / F, face row % F); a slot at or past its frame's face count holds no face (its crop was
 // zero-filled by fid_align_crops) and is written as a ZERO row -- the gathered query matrix then carries the face counts itself
 // (a rank that receives it can tell faces from empty slots: SURVEY.md 8e; reference main.py:132 iterates detected faces only)
+// src_rows != NULL (and counts == NULL): row = entry of a packed row table (fid_face_pack); src_rows[row] < 0 holds no face
 __global__ void __launch_bounds__(256) l2norm_rows(const float *__restrict__ x, int n, int dim, _Float16 *__restrict__ out,
-                                                   const int *__restrict__ counts = nullptr, int F = 1) {
+                                                   const int *__restrict__ counts = nullptr, int F = 1,
+                                                   const int *__restrict__ src_rows = nullptr) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n) return;
-    if (counts) {
+    if (counts || src_rows) {
         const int b = row / F, f = row - b * F;
-        if (f >= counts[b]) {
+        if (counts ? f >= counts[b] : src_rows[row] < 0) {
             // an EMPTY slot is a zero row whose first element is -0.0 (bit pattern 0x8000): numerically the zero row it always was (score 0,
             // never a match), but distinguishable from the all +0.0 row a DEGENERATE face of the valid prefix gets below -- so the
             // gathered matrix carries counts[] exactly (pipeline.gathered_face_counts; reference main.py:132 iterates every detected face)
@@ -169,7 +171,7 @@ int fid_l2_normalize_f16(fid_ctx *ctx, const float *emb_dev, int n, int dim, voi
     FID_REQUIRE(ctx && emb_dev && out_f16_dev && n > 0 && dim > 0, "bad args");
     std::lock_guard<std::mutex> lk(ctx->mu);
     FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
-    hipLaunchKernelGGL(fid::l2norm_rows, dim3(fid::cdiv(n, 4)), dim3(256), 0, ctx->stream, emb_dev, n, dim, (_Float16 *)out_f16_dev, (const int *)nullptr, 1);
+    hipLaunchKernelGGL(fid::l2norm_rows, dim3(fid::cdiv(n, 4)), dim3(256), 0, ctx->stream, emb_dev, n, dim, (_Float16 *)out_f16_dev, (const int *)nullptr, 1, (const int *)nullptr);
     FID_HIP(hipGetLastError());
     return FID_OK;
 }
@@ -180,7 +182,17 @@ int fid_l2_normalize_f16_slots(fid_ctx *ctx, const float *emb_dev, int n, int di
     std::lock_guard<std::mutex> lk(ctx->mu);
     FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
     hipLaunchKernelGGL(fid::l2norm_rows, dim3(fid::cdiv(n, 4)), dim3(256), 0, ctx->stream, emb_dev, n, dim, (_Float16 *)out_f16_dev,
-                       (const int *)counts_dev, faces_per_frame);
+                       (const int *)counts_dev, faces_per_frame, (const int *)nullptr);
+    FID_HIP(hipGetLastError());
+    return FID_OK;
+}
+
+int fid_l2_normalize_f16_packed(fid_ctx *ctx, const float *emb_dev, int n_rows, int dim, const int32_t *src_dev, void *out_f16_dev) {
+    FID_REQUIRE(ctx && emb_dev && out_f16_dev && src_dev && n_rows > 0 && dim > 0, "bad args");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
+    hipLaunchKernelGGL(fid::l2norm_rows, dim3(fid::cdiv(n_rows, 4)), dim3(256), 0, ctx->stream, emb_dev, n_rows, dim, (_Float16 *)out_f16_dev,
+                       (const int *)nullptr, 1, (const int *)src_dev);
     FID_HIP(hipGetLastError());
     return FID_OK;
 }
@@ -198,7 +210,7 @@ int fid_gallery_create(fid_ctx *ctx, const float *gallery, int G, int dim, fid_g
     FID_HIP(hipMalloc(&tmp, (size_t)G * dim * 4));
     FID_HIP(hipMemsetAsync(g->unit_f16, 0, (size_t)g->Gp * dim * 2, ctx->stream));
     FID_HIP(hipMemcpyAsync(tmp, gallery, (size_t)G * dim * 4, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(fid::l2norm_rows, dim3(fid::cdiv(G, 4)), dim3(256), 0, ctx->stream, (const float *)tmp, G, dim, (_Float16 *)g->unit_f16, (const int *)nullptr, 1);
+    hipLaunchKernelGGL(fid::l2norm_rows, dim3(fid::cdiv(G, 4)), dim3(256), 0, ctx->stream, (const float *)tmp, G, dim, (_Float16 *)g->unit_f16, (const int *)nullptr, 1, (const int *)nullptr);
     FID_HIP(hipStreamSynchronize(ctx->stream));
     FID_HIP(hipFree(tmp));
     *out = g;

@@ -12,7 +12,10 @@ Per step (one batch of B frames, F = max faces kept per frame = the reference's 
 Multi-GPU: frames shard by rank (independent units), weights and gallery are replicated, the only
 collective is the embedding all-gather (BASELINE.json north_star).  `FacePipeline` itself is
 single-device; `run_step_distributed` adds the collective through torch.distributed
-(backend "nccl" = RCCL on ROCm, "gloo" in the CPU tests)."""
+(backend "nccl" = RCCL on ROCm, "gloo" in the CPU tests).
+
+`PackedFacePipeline` is the same path on a dense face list: every detected face of the batch is one row
+(the reference's default max_num = 0), sum-of-faces rows instead of B * F slots."""
 from __future__ import annotations
 
 import ctypes as C
@@ -211,6 +214,156 @@ class GroupedFacePipeline(FacePipeline):
                 frames.append(faces)
             out.append(frames)
         return out
+
+
+def packed_layout(counts, cap: int, max_per_frame: int, row_cap: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The packed face layout, stated on the host (what fid_face_pack computes on the device; include/faceid.h).
+    k_b = min(max(counts[b], 0), cap) and, when max_per_frame > 0, also min(., max_per_frame).
+    -> offsets int32 [B+1]: exclusive prefix sum of k_b, offsets[B] = total faces (NOT clipped to row_cap);
+       src int32 [row_cap]: src[i] = b * cap + f of the i-th face in (frame, rank) order for i < min(total, row_cap), -1 after them
+       (faces beyond row_cap -- the last ones in that order -- are dropped)."""
+    k = np.clip(np.asarray(counts, dtype=np.int64).reshape(-1), 0, int(cap))
+    if max_per_frame > 0:
+        k = np.minimum(k, int(max_per_frame))
+    B = k.shape[0]
+    offsets = np.zeros(B + 1, np.int64)
+    offsets[1:] = np.cumsum(k)
+    n = int(min(offsets[B], row_cap))
+    frame = np.repeat(np.arange(B, dtype=np.int64), k)[:n]
+    src = np.full(int(row_cap), -1, np.int32)
+    src[:n] = frame * int(cap) + (np.arange(n, dtype=np.int64) - offsets[frame])
+    return offsets.astype(np.int32), src
+
+
+class PackedFacePipeline(FacePipeline):
+    """FacePipeline on a dense (packed) face list: EVERY face the detector returns for the batch -- `max_num = 0`, the reference's
+    default (main.py:130-134 with models/scrfd.py:159-177), or its top-`max_num` per frame -- is one row of a row table
+    (fid_face_pack / packed_layout), and alignment, recogniser, normalisation and match run on those rows instead of on
+    B x faces_per_frame slots: a crowded frame no longer sets the price of every frame of the batch.
+
+    row_cap   rows the buffers hold (<= rec.max_batch, <= 65535).  A batch with more faces loses the LAST faces of its last frames
+              (`overflow`, read after results(), says how many); a reported face is never wrong.
+    rows      "capacity": every step runs row_cap rows; fully asynchronous like FacePipeline.run_step.
+              "count":    embed() reads the batch's face total back (4 bytes; this SYNCHRONISES the stream with the host) and runs the
+                          smallest entry of `buckets` >= min(total, row_cap) rows; no face at all -> recogniser and match are skipped.
+    buckets   ascending row counts ending in row_cap (default: the multiples of 64).  The executor tunes and plans per batch size, so
+              the set of sizes it ever sees must be small and fixed; warm() runs each once.
+    More survivors than det_cap in one frame is FID_E_CAPACITY from results(), as in FacePipeline.  Rows of q / idx / score at or past
+    the rows of the last step (`n_run`) are stale.  Single device: the distributed step and step grouping know nothing of row tables."""
+
+    def __init__(self, ctx: Context, det: CompiledNet, rec: CompiledNet, *, batch: int, row_cap: int, max_num: int = 0,
+                 rows: str = "capacity", buckets: Optional[Sequence[int]] = None, conf_thres: float = 0.5, iou_thres: float = 0.4,
+                 metric: int = 0, det_cap: int = 256, q_buffer=None):
+        assert det.max_batch >= batch and rec.max_batch >= row_cap and 0 < row_cap <= 65535 and max_num >= 0
+        if rows not in ("capacity", "count"):
+            raise ValueError(f"rows must be 'capacity' or 'count', not {rows!r}")
+        self.ctx, self.det, self.rec = ctx, det, rec
+        self.B, self.F = int(batch), int(max_num)             # F: the max_num detect() hands to the post-process (0 = every survivor)
+        self.max_num, self.row_cap, self.rows = int(max_num), int(row_cap), rows
+        if buckets is None:
+            buckets = list(range(64, self.row_cap, 64)) + [self.row_cap]
+        self.buckets = [int(v) for v in buckets]
+        assert self.buckets == sorted(set(self.buckets)) and self.buckets[0] > 0 and self.buckets[-1] == self.row_cap, self.buckets
+        self.conf, self.iou, self.metric = float(conf_thres), float(iou_thres), int(metric)
+        self.in_hw = det.in_hw
+        self.post = PostProcessor(det.ctx, batch, cap=det_cap)
+        self.n_slots = self.row_cap
+        self.emb_dim = 512
+        self.offsets = ctx.empty((self.B + 1,), np.int32)
+        self.src = ctx.empty((self.row_cap,), np.int32)
+        self.crops = ctx.empty((self.row_cap, 112, 112, 3), np.uint8)
+        self.q = q_buffer if q_buffer is not None else ctx.empty((self.row_cap, self.emb_dim), np.float16)
+        self.idx = ctx.empty((self.row_cap,), np.int32)
+        self.score = ctx.empty((self.row_cap,), np.float32)
+        self._det_in = None
+        self._hv: Optional[HeadViews] = None
+        self.n_run = 0                                        # rows the last embed() ran
+        self.rec_steps = 0                                    # recogniser runs so far (a step without a face adds none in rows="count")
+        self._overflow = 0
+
+    def _rows_for(self, total: int) -> int:
+        need = min(int(total), self.row_cap)
+        return 0 if need <= 0 else next(v for v in self.buckets if v >= need)
+
+    def embed(self, frames_dev, H, W):
+        lib, h = self.ctx.lib, self.ctx.handle
+        check(lib.fid_face_pack(h, C.c_void_p(self.post.counts.ptr), self.B, self.post.cap, self.max_num,
+                                C.c_void_p(self.offsets.ptr), C.c_void_p(self.src.ptr), self.row_cap))
+        if self.rows == "count":
+            total = int(self.ctx.borrow(self.offsets.ptr + 4 * self.B, (1,), np.int32).download()[0])     # the one read-back: synchronises
+            self.n_run = self._rows_for(total)
+            if self.n_run == 0:
+                return
+        else:
+            self.n_run = self.row_cap
+        n = self.n_run
+        check(lib.fid_align_crops_packed(h, _lib._ptr(frames_dev), self.B, H, W, C.c_void_p(self.post.kps.ptr), self.post.cap,
+                                         C.c_void_p(self.src.ptr), n, C.c_void_p(self.crops.ptr), None))
+        self.rec.run_device(self.crops, n)
+        self.rec_steps += 1
+        emb_ptr, _, _ = self.rec.tensor(self.rec.low.outputs[0])
+        check(lib.fid_l2_normalize_f16_packed(h, C.c_void_p(emb_ptr), n, self.emb_dim, C.c_void_p(self.src.ptr), _lib._ptr(self.q)))
+
+    def match(self, gallery: Gallery, thresh: float, q=None, n=None, idx=None, score=None):
+        n = self.n_run if n is None else n
+        if n > 0:
+            super().match(gallery, thresh, q=q, n=n, idx=idx, score=score)
+
+    def warm(self, frames_dev, H, W, gallery: Optional[Gallery] = None, thresh: float = 0.4):
+        """Run the detector once and the recogniser (and the match, given a gallery) once per bucket, so that no later step meets a
+        row count the executor has not tuned.  Synchronises."""
+        self.detect(frames_dev, H, W)
+        lib, h = self.ctx.lib, self.ctx.handle
+        check(lib.fid_face_pack(h, C.c_void_p(self.post.counts.ptr), self.B, self.post.cap, self.max_num,
+                                C.c_void_p(self.offsets.ptr), C.c_void_p(self.src.ptr), self.row_cap))
+        for n in (self.buckets if self.rows == "count" else [self.row_cap]):
+            check(lib.fid_align_crops_packed(h, _lib._ptr(frames_dev), self.B, H, W, C.c_void_p(self.post.kps.ptr), self.post.cap,
+                                             C.c_void_p(self.src.ptr), n, C.c_void_p(self.crops.ptr), None))
+            self.rec.run_device(self.crops, n)
+            emb_ptr, _, _ = self.rec.tensor(self.rec.low.outputs[0])
+            check(lib.fid_l2_normalize_f16_packed(h, C.c_void_p(emb_ptr), n, self.emb_dim, C.c_void_p(self.src.ptr), _lib._ptr(self.q)))
+            if gallery is not None:
+                FacePipeline.match(self, gallery, thresh, n=n)
+        self.ctx.sync()
+
+    # -- results -----------------------------------------------------------------------------------
+    def _download(self):
+        """host copies of the last step: counts [B], det [B,cap,5], kps [B,cap,10], idx [row_cap], score [row_cap]"""
+        self.post.check()
+        return self.post.counts.download(), self.post.det.download(), self.post.kps.download(), self.idx.download(), self.score.download()
+
+    def results(self, gallery: Gallery):
+        """Host view of the last step: per frame the list FacePipeline.results gives -- (bbox[4], det_score, kps[5,2], name, similarity)
+        in the detector's order -- for ALL faces of the frame that found a row; sets `overflow`."""
+        counts, det, kps, idx, score = self._download()
+        cap = det.shape[1]
+        offsets, src = packed_layout(counts[:self.B], cap, self.max_num, self.row_cap)
+        kept = min(int(offsets[self.B]), self.row_cap)
+        self._overflow = int(offsets[self.B]) - kept
+        out = []
+        for b in range(self.B):
+            faces = []
+            for i in range(int(offsets[b]), min(int(offsets[b + 1]), kept)):
+                f = int(src[i]) - b * cap
+                j = int(idx[i])
+                faces.append((det[b, f, :4].copy(), float(det[b, f, 4]), kps[b, f].reshape(5, 2).copy(),
+                              gallery.names[j] if j >= 0 else "Unknown", float(score[i])))
+            out.append(faces)
+        return out
+
+    @property
+    def overflow(self) -> int:
+        """faces of the last results() that found no row (batch total - row_cap, 0 if they all fit)"""
+        return self._overflow
+
+    def embeddings(self) -> Tuple[np.ndarray, np.ndarray]:
+        """Raw (un-normalised) fp32 embeddings of the last step, [faces kept, 512] in row order, and offsets [B+1] (packed_layout:
+        frame b owns rows offsets[b] : offsets[b+1], cut at the number of rows returned)."""
+        offsets, _ = packed_layout(self.post.counts.download()[:self.B], self.post.cap, self.max_num, self.row_cap)
+        kept = min(int(offsets[self.B]), self.row_cap, self.n_run)
+        if kept == 0:
+            return np.zeros((0, self.emb_dim), np.float32), offsets
+        return self.rec.read(self.rec.low.outputs[0], kept).reshape(kept, -1), offsets
 
 
 def calibrate_detector_bias(ctx: Context, net, params, frames: np.ndarray, target: int = 48, max_batch: int = 8):
@@ -446,6 +599,9 @@ def run_step_distributed(pipe, frames_dev, H, W, gallery, thresh, q_local, q_all
     are sized for a full group, a partial group uses their first rows (every rank holds the same number of steps).  Returns True when results
     were written.
     """
+    if isinstance(pipe, PackedFacePipeline):
+        # its rows are not B x F slots: the other ranks' per-frame offsets would have to travel too (a second small gather)
+        raise TypeError("run_step_distributed works on face slots (FacePipeline / GroupedFacePipeline); a PackedFacePipeline is single-device")
     r, world = dist.get_rank(), dist.get_world_size()
     n = pipe.n_slots
     grouped = hasattr(pipe, "collect")
