@@ -56,6 +56,10 @@ class CompiledNet:
                                                 ms.ctypes.data_as(_lib.c_f32_p)))
         return ms
 
+    def set_sub_batch(self, n: int):
+        """images per depth-first pass of run / run_device (fid_net_set_sub_batch; 0 = every layer on the whole batch)"""
+        check(self.ctx.lib.fid_net_set_sub_batch(self.handle, int(n)))
+
     # -- tensors ----------------------------------------------------------------------------
     def tensor(self, name: str):
         """(device pointer, (H, W, C, C_stored), dtype) of a tensor of the last run."""

@@ -1,0 +1,143 @@
+"""Shared pieces of the kernel-family GPU tests (test_gpu_conv_families.py, test_gpu_batch_shapes.py): the layer stacks, the translation of a
+test's generation code into the autotuner hooks FID_FORCE_GEN / FID_FORCE_NS, the check of WHICH family ran, and the activation-slot guard
+(poison the rows at or beyond the batch of a net that runs below its max_batch, check them afterwards).  Plain module, no fixtures; the slot
+arithmetic is pure Python on lower()'s tensor table, so tests/test_slot_guard_cpu.py checks it without a GPU."""
+import numpy as np
+
+from scrfd_arcface_facerecognition_amd.archs import Conv, Net
+from scrfd_arcface_facerecognition_amd.lower import OP_CONV, OP_LATFPN, OP_STEMBLOCK
+
+
+# words of an op record that name a second tensor (csrc/net.h)
+W_TYPE, W_DST, W_X_DST2, W_L_LAT, W_S_DST2, W_X_SRC2, W_X_W2OFF, T_SLOT = 0, 2, 20, 22, 24, 23, 29, 5
+
+
+def force_family(monkeypatch, code):
+    """a test's generation code -> FID_FORCE_GEN / FID_FORCE_NS (59 = generation 5 with register-staged producers; codes >= 900 and the
+    two-digit ring / tile codes carry the variant in their last digits; every other code is the generation itself)"""
+    if code == 59:
+        monkeypatch.setenv("FID_FORCE_GEN", "5")
+        monkeypatch.setenv("FID_PC_RS", "1")
+    elif code >= 900:
+        monkeypatch.setenv("FID_FORCE_GEN", str(code // 100))
+        monkeypatch.setenv("FID_FORCE_NS", str(code % 100))
+    elif code in (25, 51, 91, 92, 93, 94, 96, 97, 98):
+        monkeypatch.setenv("FID_FORCE_GEN", str(code // 10))
+        monkeypatch.setenv("FID_FORCE_NS", str(code % 10))
+    else:
+        monkeypatch.setenv("FID_FORCE_GEN", str(code))
+
+
+def forced_ran(cn, code, batch=None):
+    """ops of the net whose pick is the kernel family the test forced (code = the test's generation code: FID_FORCE_GEN, or
+    FID_FORCE_GEN * 10 + FID_FORCE_NS for the ring / tile variants).  FID_FORCE_GEN only restricts the candidates where the family
+    applies; a test that asserted nothing about the pick would pass on another family's result.  batch: only the picks made for that
+    batch size (a net that ran several)."""
+    def hit(p):
+        if code in (25, 51):
+            return p["gen"] == code // 10 and p["ns"] == (5 if code == 25 else 1)
+        if code == 59:
+            return p["gen"] == 5
+        if code in (91, 92):
+            return p["gen"] == 9 and p["ns"] not in (1, 4, 6) and p["bm"] // 256 == code % 10
+        if code == 93:
+            return p["gen"] == 9 and p["ns"] == 1
+        if code == 94:
+            return p["gen"] == 9 and p["ns"] == 4
+        if code in (96, 97):                                    # conv_ks: one / two items per workgroup (plan tile 256 / 512)
+            return p["gen"] == 9 and p["ns"] == 6 and p["bm"] == (256 if code == 96 else 512)
+        if code == 98:                                          # conv_ks on x-packed STRIP tiles
+            return p["gen"] == 9 and p["ns"] == 7
+        if code in (909, 929, 939):                             # conv_wr on STRIP tiles: one tile x 64 couts / a pair x 128 couts / one tile x 128 couts
+            return p["gen"] == 9 and p["ns"] == 8 and (p["bm"], p["bn"]) == {909: (256, 64), 929: (512, 128), 939: (256, 128)}[code]
+        if code == 910:                                         # conv_wr on STRIP tiles, the layer's weights resident
+            return p["gen"] == 9 and p["ns"] == 9
+        return p["gen"] == code
+    return [p["name"] for p in cn.plans() if hit(p) and (batch is None or p["batch"] == batch)]
+
+
+def stack(hw, chans, res=True):
+    net = Net("t", hw, 127.5, 1.0 / 128.0)
+    net.add(Conv("s", "input", 3, 64, act="relu"))
+    src, cin = "s", 64
+    for i, c in enumerate(chans):
+        net.add(Conv(f"a{i}", src, cin, c, act="prelu", pre_bn=(i == 1)))
+        net.add(Conv(f"b{i}", f"a{i}", c, c, act="relu", res=f"a{i}" if res else None))
+        src, cin = f"b{i}", c
+    net.outputs = [src]
+    return net
+
+
+# ---- activation slots: rows at or beyond the batch ------------------------------------------------------------------------------------
+
+# both as fp16 and as fp32 pairs: 0x7BFF = 65504 / a large finite value, 0x7E00 = NaN / NaN
+POISON = {"max": 0x7BFF, "nan": 0x7E00}
+
+
+def slot_table(low):
+    """(slot of every tensor, bytes per image of every tensor, bytes per image of every slot) from lower()'s tensor table.  Column 5 is the
+    slot (a view's record already names its base's slot), a tensor's image is H x W x Cp elements of 2 (fp16) or 4 (fp32, dtype 1) bytes,
+    every tensor of a slot starts at the slot's base, and a slot's image is the largest of its tensors' (csrc/net.hip, fid_net_create)."""
+    t_slot, t_bytes, s_bytes = [], [], {}
+    for C_, Cp, H, W, dtype, slot, _, _ in (tuple(int(v) for v in r) for r in low.tensors):
+        b = H * W * Cp * (4 if dtype == 1 else 2)
+        t_slot.append(slot)
+        t_bytes.append(b)
+        s_bytes[slot] = max(s_bytes.get(slot, 0), b)
+    return t_slot, t_bytes, s_bytes
+
+
+def guard_regions(low, b, max_batch):
+    """{slot: (first guard byte, end)}: the bytes of a slot no image below b of ANY of its tensors occupies, up to the allocation's end"""
+    _, _, s_bytes = slot_table(low)
+    return {s: (b * n, max_batch * n) for s, n in s_bytes.items()}
+
+
+def own_data_tensors(low):
+    """names of the tensors that still hold their own rows after a run: the last tensor written into its slot (earlier tenants were
+    overwritten), except where that writer is a block-shortcut conv the consuming conv may absorb (then it does not run at all)"""
+    names = {i: n for n, i in low.tensor_id.items()}
+    last = {}
+    for r in low.ops:
+        kind = int(r[W_TYPE])
+        dsts = [int(r[W_DST])]
+        for op, word in ((OP_CONV, W_X_DST2), (OP_STEMBLOCK, W_S_DST2), (OP_LATFPN, W_L_LAT)):     # second outputs: tensor id + 1
+            if kind == op and r[word] > 0:
+                dsts.append(int(r[word]) - 1)
+        maybe_skipped = kind == OP_CONV and r[W_X_SRC2] == 0 and r[W_X_W2OFF] > 0                 # word 29 of a shortcut op: its consumer + 1
+        for d in dsts:
+            last[int(low.tensors[d][T_SLOT])] = None if maybe_skipped else d
+    return sorted(names[d] for d in last.values() if d is not None)
+
+
+class SlotGuard:
+    """The rows at or beyond batch b of every activation slot of a CompiledNet built for more: poison() fills them with a 16-bit pattern,
+    check() asserts that a run left every byte of them alone.  A kernel only receives the tensor pointer and the batch: a store into row b
+    is a heap overrun on a net whose max_batch is b."""
+
+    def __init__(self, ctx, cn, b, pattern):
+        assert 0 < b < cn.max_batch
+        self.ctx, self.cn, self.b, self.word = ctx, cn, b, np.uint16(POISON[pattern])
+        t_slot, _, _ = slot_table(cn.low)
+        by_id = {i: n for n, i in cn.low.tensor_id.items()}
+        self.regions = []
+        for slot, (lo, hi) in sorted(guard_regions(cn.low, b, cn.max_batch).items()):
+            ptr, _, _ = cn.tensor(by_id[t_slot.index(slot)])          # any tensor of the slot: all start at its base
+            assert lo % 2 == 0 and hi > lo
+            self.regions.append((slot, lo, ctx.borrow(ptr + lo, ((hi - lo) // 2,), np.uint16)))
+
+    def poison(self):
+        for _, _, buf in self.regions:
+            buf.upload(np.full(buf.shape, self.word, np.uint16))
+        return self
+
+    def check(self, what=""):
+        for slot, lo, buf in self.regions:
+            got = buf.download()
+            bad = np.flatnonzero(got != self.word)
+            if bad.size:
+                byte = lo + 2 * int(bad[0])
+                per = lo // self.b
+                raise AssertionError(f"{what}: slot {slot} written beyond batch {self.b}: first changed byte {byte} (image row {byte // per}, "
+                                     f"offset {byte % per} of {per}), {bad.size} of {got.size} guard words changed, "
+                                     f"0x{int(got[bad[0]]):04x} instead of 0x{int(self.word):04x}")

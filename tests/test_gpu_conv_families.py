@@ -7,6 +7,8 @@ from oracle import align, nets as onets
 from scrfd_arcface_facerecognition_amd import archs
 from scrfd_arcface_facerecognition_amd.archs import Conv, Net
 
+from family_helpers import force_family, forced_ran, stack
+
 pytestmark = pytest.mark.gpu
 
 
@@ -16,45 +18,6 @@ def ctx():
     c = Context(0)
     yield c
     c.close()
-
-
-def forced_ran(cn, code):
-    """ops of the net whose pick is the kernel family the test forced (code = the test's generation code: FID_FORCE_GEN, or
-    FID_FORCE_GEN * 10 + FID_FORCE_NS for the ring / tile variants).  FID_FORCE_GEN only restricts the candidates where the family
-    applies; a test that asserted nothing about the pick would pass on another family's result."""
-    def hit(p):
-        if code in (25, 51):
-            return p["gen"] == code // 10 and p["ns"] == (5 if code == 25 else 1)
-        if code == 59:
-            return p["gen"] == 5
-        if code in (91, 92):
-            return p["gen"] == 9 and p["ns"] not in (1, 4, 6) and p["bm"] // 256 == code % 10
-        if code == 93:
-            return p["gen"] == 9 and p["ns"] == 1
-        if code == 94:
-            return p["gen"] == 9 and p["ns"] == 4
-        if code in (96, 97):                                    # conv_ks: one / two items per workgroup (plan tile 256 / 512)
-            return p["gen"] == 9 and p["ns"] == 6 and p["bm"] == (256 if code == 96 else 512)
-        if code == 98:                                          # conv_ks on x-packed STRIP tiles
-            return p["gen"] == 9 and p["ns"] == 7
-        if code in (909, 929, 939):                             # conv_wr on STRIP tiles: one tile x 64 couts / a pair x 128 couts / one tile x 128 couts
-            return p["gen"] == 9 and p["ns"] == 8 and (p["bm"], p["bn"]) == {909: (256, 64), 929: (512, 128), 939: (256, 128)}[code]
-        if code == 910:                                         # conv_wr on STRIP tiles, the layer's weights resident
-            return p["gen"] == 9 and p["ns"] == 9
-        return p["gen"] == code
-    return [p["name"] for p in cn.plans() if hit(p)]
-
-
-def stack(hw, chans, res=True):
-    net = Net("t", hw, 127.5, 1.0 / 128.0)
-    net.add(Conv("s", "input", 3, 64, act="relu"))
-    src, cin = "s", 64
-    for i, c in enumerate(chans):
-        net.add(Conv(f"a{i}", src, cin, c, act="prelu", pre_bn=(i == 1)))
-        net.add(Conv(f"b{i}", f"a{i}", c, c, act="relu", res=f"a{i}" if res else None))
-        src, cin = f"b{i}", c
-    net.outputs = [src]
-    return net
 
 
 # 25 = generation 2 with ns = 5 (fragment prefetch across K-steps), 51 = generation 5 with the weights two steps ahead,
@@ -71,17 +34,7 @@ def stack(hw, chans, res=True):
                                             ((14, 14), (128, 128), 5), ((20, 20), (64, 96), 4), ((20, 20), (224, 224), 3)])
 def test_conv_family(ctx, monkeypatch, gen, hw, chans, batch):
     from scrfd_arcface_facerecognition_amd.engine import CompiledNet
-    if gen == 59:
-        monkeypatch.setenv("FID_FORCE_GEN", "5")
-        monkeypatch.setenv("FID_PC_RS", "1")
-    elif gen >= 900:
-        monkeypatch.setenv("FID_FORCE_GEN", str(gen // 100))
-        monkeypatch.setenv("FID_FORCE_NS", str(gen % 100))
-    elif gen in (25, 51, 91, 92, 93, 94, 96, 97, 98):
-        monkeypatch.setenv("FID_FORCE_GEN", str(gen // 10))
-        monkeypatch.setenv("FID_FORCE_NS", str(gen % 10))
-    else:
-        monkeypatch.setenv("FID_FORCE_GEN", str(gen))
+    force_family(monkeypatch, gen)
     net = stack(hw, chans)
     P = archs.synth_params(net, seed=9)
     images = np.random.default_rng(3).integers(0, 256, (batch,) + hw + (3,), dtype=np.uint8)
@@ -103,9 +56,7 @@ def test_conv_family(ctx, monkeypatch, gen, hw, chans, batch):
 @pytest.mark.parametrize("chans,batch", [((128, 128), 9), ((64, 192), 3), ((256, 64), 1), ((128, 512), 64), ((64, 64), 4)])
 def test_conv_mosaic_7x7(ctx, monkeypatch, gen, chans, batch):
     from scrfd_arcface_facerecognition_amd.engine import CompiledNet
-    monkeypatch.setenv("FID_FORCE_GEN", str(gen // 10) if gen > 11 else str(gen))
-    if gen > 11:
-        monkeypatch.setenv("FID_FORCE_NS", str(gen % 10))
+    force_family(monkeypatch, gen)
     net = stack((7, 7), chans)
     P = archs.synth_params(net, seed=31)
     images = np.random.default_rng(33).integers(0, 256, (batch, 7, 7, 3), dtype=np.uint8)
@@ -134,8 +85,7 @@ def test_conv_mosaic_7x7(ctx, monkeypatch, gen, chans, batch):
                                             ((20, 20), (96, 64), 5), ((20, 20), (224, 224), 3)])
 def test_conv_strip(ctx, monkeypatch, gen, hw, chans, batch):
     from scrfd_arcface_facerecognition_amd.engine import CompiledNet
-    monkeypatch.setenv("FID_FORCE_GEN", str(gen // (100 if gen >= 900 else 10)))
-    monkeypatch.setenv("FID_FORCE_NS", str(gen % (100 if gen >= 900 else 10)))
+    force_family(monkeypatch, gen)
     net = stack(hw, chans)
     P = archs.synth_params(net, seed=41)
     images = np.random.default_rng(43).integers(0, 256, (batch,) + hw + (3,), dtype=np.uint8)
