@@ -44,25 +44,39 @@ struct ConvArgs {
     unsigned in_bytes, w_bytes;
 };
 
-// fills the derived fields (T, nchunk, ksteps, tiles, split-K plan) and launches; `partial_ws`
-// must hold ksplit*M*Cout_p floats when the plan splits K (query with conv_plan first).
+// A conv kernel pick: the six numbers of a plan-file line and of CompiledNet.plans().  Which kernel a tuple names is decided by the variant
+// table of conv.hip alone (conv_variant); nothing else decodes gen / ns / bm / bn.
 struct ConvPlan {
     int bm, bn, bk, ksplit;
-    int gen;   // 0 = conv_direct, 1 = register-staged double buffer, 2 = LDS-DMA ring, 3 = conv_chunked, 4 = conv_pp, 5 = conv_pc (bn = couts per work item), 6 = LDS-DMA ring with producer waves, 7 = conv_pcr, 8 = conv_pc2, 9 = conv_wr, 10 = conv_s2, 11 = conv_gw
-    int ns;    // ring slots (gen 2); 5 = 4 slots + fragment prefetch across K-steps
+    int gen, ns;   // kernel family and its variant: the key of the variant table (DESIGN.md lists the variants and their tuples)
     size_t partial_bytes;
 };
-ConvPlan conv_plan(const ConvArgs &a, int num_cus, bool allow_split);
-// every kernel/tile/split combination worth timing for this conv (gen 0 = conv_direct); used by the
-// executor's per-layer autotuner (net.hip) -- "measure, don't guess"
+struct ConvVariant {          // one kernel variant the library can launch: a row of the table in conv.hip
+    const char *name;         // short and stable: logs, documents, tests
+    int gen, ns, bm, bn;      // the plan tuples it names: ns = -1 / bm = 0 / bn = 0 match any
+    int alt;                  // alternate weight packing it wants in ConvArgs::w_alt (0 = none); repack.hip builds it
+    bool rev;                 // honours ConvArgs::rev
+    int force_ns;             // the FID_FORCE_NS value that selects it (-1: none)
+    int base;                 // fused-shortcut variants: the generation the executor launches, same ns, on the fused argument block (-1: not fused)
+    int (*launch)(fid_ctx *, const ConvArgs &, const ConvPlan &);            // null: fused shortcut (launches through `base`)
+    long long (*wgs)(const ConvArgs &, const ConvPlan &, int num_cus);       // workgroups of the launch, or null (not modelled)
+};
+const ConvVariant *conv_variant(const ConvPlan &plan);                       // null: the tuple names nothing
+inline const char *conv_plan_name(const ConvPlan &plan) { const ConvVariant *v = conv_variant(plan); return v ? v->name : "?"; }
+inline bool conv_fuses_shortcut(const ConvPlan &plan) { const ConvVariant *v = conv_variant(plan); return v && v->base >= 0; }
+ConvPlan conv_fused_plan(ConvPlan base);      // the fused-shortcut pick that launches `base` (a candidate of the fused argument block)
+ConvPlan conv_base_plan(ConvPlan fused);      // ... and back
+bool conv_force_match(const ConvPlan &plan, int force_gen, int force_ns);     // the autotuner's test hooks FID_FORCE_GEN / FID_FORCE_NS: does the plan pass (negative: filter not set)?
+
+ConvPlan conv_plan(const ConvArgs &a, int num_cus, bool allow_split);            // the implicit GEMM's heuristic pick
+ConvPlan conv_plan_untuned(const ConvArgs &a, int num_cus, bool allow_split);    // what runs without the autotuner: conv_direct where it applies, else conv_plan
+// every kernel/tile/split combination worth timing for this conv; used by the executor's per-layer autotuner (net.hip) -- "measure, don't guess"
 #include <vector>
 std::vector<ConvPlan> conv_candidates(const ConvArgs &a, int num_cus, bool allow_split);
-int conv_launch(fid_ctx *ctx, ConvArgs a, const ConvPlan &plan);
+int conv_launch(fid_ctx *ctx, ConvArgs a, const ConvPlan &plan);      // `a.partial` must hold ksplit*M*Cout_p floats when the plan splits K (the candidate's partial_bytes)
 float conv_plan_cu_share(const ConvArgs &a, const ConvPlan &plan, int num_cus);      // fraction of the CUs the launch occupies (1: all / not modelled)
-// does the kernel `plan` names honour ConvArgs::rev?
-inline bool conv_walks_reverse(const ConvPlan &plan) { return plan.gen == 9; }
-// alternate weight packing a plan's kernel wants in ConvArgs::w_alt (0 = none); repack.hip builds it
-int plan_alt_kind(const ConvPlan &plan);
+inline bool conv_walks_reverse(const ConvPlan &plan) { const ConvVariant *v = conv_variant(plan); return v && v->rev; }
+int plan_alt_kind(const ConvPlan &plan);      // ConvVariant::alt of the plan's variant (0 = none)
 size_t repack_bytes(int kind, int Cout_p, int Cin_p, int taps = 9);
 int repack_weights(fid_ctx *ctx, int kind, const void *src, void *dst, int Cout_p, int Cin_p, int taps = 9);
 

@@ -759,13 +759,37 @@ int launch_pcg(fid_ctx *ctx, const ConvArgs &a) {
 
 }  // namespace
 
-static bool dma_have(int bm, int bn, int bk) {
-    if (bk == 64) return (bm == 128 && (bn == 128 || bn == 64)) || (bm == 64 && bn == 64);
-    return bm == 128 && (bn == 128 || bn == 96 || bn == 64 || bn == 32);
+// Every instance of the implicit-GEMM kernels (generations 1, 2 and 6) in the order conv_candidates lists them (per BK; it decides ties in the
+// autotuner).  ns = 5: four ring slots + fragment prefetch across K-steps; generation 1 has no ring (its candidates carry ns = 4).
+struct GemmTile { int gen, bm, bn, bk, ns; int (*launch)(fid_ctx *, const ConvArgs &); };
+static const GemmTile GEMM_TILES[] = {
+    {1, 128, 128, 64, 4, launch_cfg<128, 128, 64, 2, 2>},          {1, 128, 64, 64, 4, launch_cfg<128, 64, 64, 2, 2>},          {1, 64, 64, 64, 4, launch_cfg<64, 64, 64, 2, 2>},
+    {2, 128, 128, 64, 4, launch_dma<128, 128, 64, 4, 2, 2>},       {2, 128, 64, 64, 4, launch_dma<128, 64, 64, 4, 2, 2>},       {2, 64, 64, 64, 4, launch_dma<64, 64, 64, 4, 2, 2>},
+    {2, 128, 128, 64, 3, launch_dma<128, 128, 64, 3, 2, 2>},       {2, 128, 64, 64, 3, launch_dma<128, 64, 64, 3, 2, 2>},       {2, 64, 64, 64, 3, launch_dma<64, 64, 64, 3, 2, 2>},
+    {2, 128, 128, 64, 5, launch_dma<128, 128, 64, 4, 2, 2, true>}, {2, 128, 64, 64, 5, launch_dma<128, 64, 64, 4, 2, 2, true>}, {2, 64, 64, 64, 5, launch_dma<64, 64, 64, 4, 2, 2, true>},
+    {6, 128, 128, 64, 4, launch_pcg<128, 128, 64, 4, 2, 2>},       {6, 128, 64, 64, 4, launch_pcg<128, 64, 64, 4, 2, 2>},       {6, 64, 64, 64, 4, launch_pcg<64, 64, 64, 4, 2, 2>},
+    {6, 128, 64, 64, 3, launch_pcg<128, 64, 64, 3, 2, 2>},         {6, 64, 64, 64, 3, launch_pcg<64, 64, 64, 3, 2, 2>},
+    {1, 128, 128, 32, 4, launch_cfg<128, 128, 32, 2, 2>},          {1, 128, 96, 32, 4, launch_cfg<128, 96, 32, 2, 2>},          {1, 128, 64, 32, 4, launch_cfg<128, 64, 32, 2, 2>},
+    {1, 128, 32, 32, 4, launch_cfg<128, 32, 32, 4, 1>},
+    {2, 128, 128, 32, 4, launch_dma<128, 128, 32, 4, 2, 2>},       {2, 128, 96, 32, 4, launch_dma<128, 96, 32, 4, 2, 2>},       {2, 128, 64, 32, 4, launch_dma<128, 64, 32, 4, 2, 2>},
+    {2, 128, 32, 32, 4, launch_dma<128, 32, 32, 4, 4, 1>},
+    {6, 128, 128, 32, 4, launch_pcg<128, 128, 32, 4, 2, 2>},       {6, 128, 96, 32, 4, launch_pcg<128, 96, 32, 4, 2, 2>},       {6, 128, 64, 32, 4, launch_pcg<128, 64, 32, 4, 2, 2>},
+};
+
+static const GemmTile *gemm_tile(int gen, int bm, int bn, int bk, int ns) {
+    for (const GemmTile &t : GEMM_TILES)
+        if (t.gen == gen && t.bm == bm && t.bn == bn && t.bk == bk && t.ns == ns) return &t;
+    return nullptr;
+}
+// a pick of one of the halo-patch kernels (32-channel K chunks, no split-K; conv_direct: no tile)
+static ConvPlan patch_plan(int gen, int bm, int bn, int ns = 0) {
+    ConvPlan d{};
+    d.gen = gen; d.bm = bm; d.bn = bn; d.bk = bm ? 32 : 0; d.ksplit = 1; d.ns = ns;
+    return d;
 }
 
 ConvPlan conv_plan(const ConvArgs &a, int num_cus, bool allow_split) {
-    if (a.out2) { ConvPlan d{}; d.gen = 10; d.ksplit = 1; d.bm = 128; d.bn = a.w_rows; d.bk = 32; return d; }
+    if (a.out2) return patch_plan(10, 128, a.w_rows);
     ConvPlan p{};
     static const bool use_v1 = getenv("FID_CONV_V1") != nullptr;
     auto tiles = [&](int bm, int bn) { return (long long)cdiv(a.M, bm) * cdiv(a.Cout_p, bn); };
@@ -808,9 +832,7 @@ ConvPlan conv_plan(const ConvArgs &a, int num_cus, bool allow_split) {
         int bm = 0, bn = 0, ks = 0, ns = 0;
         const int n = sscanf(f, "%d,%d,%d,%d", &bm, &bn, &ks, &ns);
         if (n >= 3) {
-            const bool have = p.gen == 2 ? dma_have(bm, bn, p.bk)
-                              : (p.bk == 64 ? ((bm == 128 && (bn == 128 || bn == 64)) || (bm == 64 && bn == 64))
-                                            : (bm == 128 && (bn == 128 || bn == 96 || bn == 64 || bn == 32)));
+            const bool have = gemm_tile(p.gen, bm, bn, p.bk, 4) != nullptr;
             if (have) { p.bm = bm; p.bn = bn; }
             if (ks >= 1 && allow_split && !(a.flags & CF_ARGMAX)) p.ksplit = std::max(1, std::min(ks, ksteps / 2));
             if (n >= 4 && ns >= 3 && ns <= 4 && p.bk == 64) p.ns = ns;
@@ -820,94 +842,55 @@ ConvPlan conv_plan(const ConvArgs &a, int num_cus, bool allow_split) {
     return p;
 }
 
-static std::vector<ConvPlan> conv_candidates_all(const ConvArgs &a, int num_cus, bool allow_split);
-
-std::vector<ConvPlan> conv_candidates(const ConvArgs &a, int num_cus, bool allow_split) {
-    std::vector<ConvPlan> all = conv_candidates_all(a, num_cus, allow_split);
-    if (!a.in2) return all;
-    std::vector<ConvPlan> only;                      // fused shortcut (extra K-steps on a second tensor): the LDS-DMA implicit GEMM ...
-    for (const ConvPlan &c : all)
-        if (c.gen == 2 && a.Cin2_p % c.bk == 0) only.push_back(c);
-    if (conv_s2_applicable(a)) {                     // ... and the parity-plane stride-2 kernel with the shortcut as one more step per item (ns = 10)
-        ConvPlan d{};
-        d.gen = 10; d.ksplit = 1; d.bm = 128; d.bn = a.Cout_p; d.bk = 32; d.ns = 10;
-        only.push_back(d);
-    }
-    return only;
-}
-
 static std::vector<ConvPlan> conv_candidates_all(const ConvArgs &a, int num_cus, bool allow_split) {
-    if (a.out2) {                                   // fused shortcut + stride-2 conv: one kernel takes it
-        std::vector<ConvPlan> only;
-        if (conv_s2_applicable(a)) { ConvPlan d{}; d.gen = 10; d.ksplit = 1; d.bm = 128; d.bn = a.w_rows; d.bk = 32; only.push_back(d); }
-        return only;
-    }
     std::vector<ConvPlan> out;
-    if (conv_direct_applicable(a)) { ConvPlan d{}; d.gen = 0; d.ksplit = 1; out.push_back(d); }
+    auto cand = [&](int gen, int bm, int bn, int ns = 0) { out.push_back(patch_plan(gen, bm, bn, ns)); };
+    if (a.out2) {                                   // fused shortcut + stride-2 conv: one kernel takes it
+        if (conv_s2_applicable(a)) cand(10, 128, a.w_rows);
+        return out;
+    }
+    if (conv_direct_applicable(a)) cand(0, 0, 0);
     if (conv_chunked_applicable(a) && !getenv("FID_NO_CHUNKED")) {
-        ConvPlan d{};
-        d.gen = 3; d.ksplit = 1; d.bm = 256; d.bk = 32;
-        d.bn = 64; out.push_back(d);
-        if (a.Cout_p % 96 == 0) { d.bn = 96; out.push_back(d); }
+        cand(3, 256, 64);
+        if (a.Cout_p % 96 == 0) cand(3, 256, 96);
     }
-    if (conv_pcr_applicable(a)) { ConvPlan d{}; d.gen = 7; d.ksplit = 1; d.bm = 256; d.bn = 64; d.bk = 32; out.push_back(d); }
-    if (conv_pc2_applicable(a)) { ConvPlan d{}; d.gen = 8; d.ksplit = 1; d.bm = 512; d.bn = 64; d.bk = 32; out.push_back(d); }
-    if (conv_s2_applicable(a)) { ConvPlan d{}; d.gen = 10; d.ksplit = 1; d.bm = 128; d.bn = a.Cout_p; d.bk = 32; out.push_back(d); }
-    if (conv_gw_applicable(a)) {
-        ConvPlan d{};
-        d.gen = 11; d.ksplit = 1; d.bk = 32;
+    if (conv_pcr_applicable(a)) cand(7, 256, 64);
+    if (conv_pc2_applicable(a)) cand(8, 512, 64);
+    if (conv_s2_applicable(a)) cand(10, 128, a.Cout_p);
+    if (conv_gw_applicable(a))
         for (int bm : {128, 64})
-            for (int bn : {256, 128}) {
-                if (bn == 256 && a.Cout_p <= 128) continue;
-                d.bm = bm; d.bn = bn; out.push_back(d);
-            }
-    }
+            for (int bn : {256, 128})
+                if (bn != 256 || a.Cout_p > 128) cand(11, bm, bn);
     if (conv_wr_applicable(a)) {
-        ConvPlan d{};
-        d.gen = 9; d.ksplit = 1; d.bk = 32;
-        d.bm = 512; d.bn = 128; out.push_back(d);      // a pair of tiles x 128 couts
-        d.bm = 256; d.bn = 64; out.push_back(d);       // one tile x 64 couts (few tiles: more items)
-        d.ns = 4; out.push_back(d); d.ns = 0;          // ... with the patches three steps ahead (small batches: one workgroup per CU)
-        if (conv_wr_resident_ok(a)) { d.bm = 256; d.bn = a.Cout_p; d.ns = 1; out.push_back(d); }   // the layer's weights resident in registers
+        cand(9, 512, 128);                             // a pair of tiles x 128 couts
+        cand(9, 256, 64);                              // one tile x 64 couts (few tiles: more items)
+        cand(9, 256, 64, 4);                           // ... with the patches three steps ahead (small batches: one workgroup per CU)
+        if (conv_wr_resident_ok(a)) cand(9, 256, a.Cout_p, 1);   // the layer's weights resident in registers
         if (conv_strip_ok(a)) {                        // the same on x-packed STRIP tiles (round 5): ns = 8 streaming, 9 resident
-            d.ns = 8; d.bm = 512; d.bn = 128; out.push_back(d);
-            d.bm = 256; d.bn = 64; out.push_back(d);
-            if (a.Cout_p > 64) { d.bm = 256; d.bn = 128; out.push_back(d); }     // one tile x 128 couts (eight waves)
-            if (conv_wr_resident_ok(a)) { d.bm = 256; d.bn = a.Cout_p; d.ns = 9; out.push_back(d); }
-            d.ns = 0;
+            cand(9, 512, 128, 8);
+            cand(9, 256, 64, 8);
+            if (a.Cout_p > 64) cand(9, 256, 128, 8);   // one tile x 128 couts (eight waves)
+            if (conv_wr_resident_ok(a)) cand(9, 256, a.Cout_p, 9);
         }
         if (conv_ks_applicable(a)) {                   // one tile x 64 couts, the K axis split over two wave groups (conv_ks.hip)
-            d.bm = 256; d.bn = 64; d.ns = 6; out.push_back(d);
+            cand(9, 256, 64, 6);
             const int items = conv_ks_items(a);        // few items: also on half the CUs with two or more items per workgroup (tile 512; fewer CUs for longer, FID_TUNE_SHARE)
-            if (items >= 2 && items <= 2 * num_cus) { d.bm = 512; out.push_back(d); }
-            if (conv_ks_strip_applicable(a)) { d.bm = 256; d.bn = 64; d.ns = 7; out.push_back(d); }   // ... on x-packed STRIP tiles
+            if (items >= 2 && items <= 2 * num_cus) cand(9, 512, 64, 6);
+            if (conv_ks_strip_applicable(a)) cand(9, 256, 64, 7);   // ... on x-packed STRIP tiles
         }
-    }
-    else if (conv_ks_applicable(a)) {                  // 7x7 maps: four images per 16x16 tile (conv_ks.hip, MOSAIC)
-        ConvPlan d{};
-        d.gen = 9; d.ksplit = 1; d.bk = 32; d.bm = 256; d.bn = 64; d.ns = 6; out.push_back(d);
-    }
+    } else if (conv_ks_applicable(a)) cand(9, 256, 64, 6);       // 7x7 maps: four images per 16x16 tile (conv_ks.hip, MOSAIC)
     if (conv_pc_applicable(a)) {
-        ConvPlan d{};
-        d.gen = 5; d.ksplit = 1; d.bm = 256; d.bk = 32;
-        if (a.flags & CF_OUT_F32) { d.bn = 32; d.ns = 0; out.push_back(d); }
+        if (a.flags & CF_OUT_F32) cand(5, 256, 32);
         else {
-        d.bn = 64; d.ns = 0; out.push_back(d);
-        // weights two steps ahead instead of patches: measured equal or 1-2 % slower everywhere; kept for tests / experiments
-        if (getenv("FID_FORCE_NS")) { d.ns = 1; out.push_back(d); }
-        d.ns = 0;
-        if (a.Cout_p % 96 == 0) { d.bn = 96; out.push_back(d); }
+            cand(5, 256, 64);
+            // weights two steps ahead instead of patches: measured equal or 1-2 % slower everywhere; kept for tests / experiments
+            if (getenv("FID_FORCE_NS")) cand(5, 256, 64, 1);
+            if (a.Cout_p % 96 == 0) cand(5, 256, 96);
         }
     }
-    if (conv_pp_applicable(a)) {
-        ConvPlan d{};
-        d.gen = 4; d.ksplit = 1; d.bm = 512; d.bk = 32;
-        for (int cb : {32, 48, 64}) {
-            if (cb > 32 && cdiv(a.Cout_p, cb) * cb > cdiv(a.Cout_p, 32) * 32) continue;   // would pad more couts than cb = 32
-            d.bn = cb;
-            out.push_back(d);
-        }
-    }
+    if (conv_pp_applicable(a))
+        for (int cb : {32, 48, 64})
+            if (cb == 32 || cdiv(a.Cout_p, cb) * cb <= cdiv(a.Cout_p, 32) * 32) cand(4, 512, cb);   // (not where cb would pad more couts than 32)
     const int bk = (a.Cin_p % 64 == 0) ? 64 : 32;
     const int ksteps = a.kh * a.kw * (a.Cin_p / bk);
     auto tiles = [&](int bm, int bn) { return (long long)cdiv(a.M, bm) * cdiv(a.Cout_p, bn); };
@@ -931,62 +914,27 @@ static std::vector<ConvPlan> conv_candidates_all(const ConvArgs &a, int num_cus,
     // wave) and 5-12 % faster only on the 64-face 14x14 / 7x7 layers, which the halo-patch kernels serve better anyway.
     const char *fg6 = getenv("FID_FORCE_GEN");
     const bool gemm_pc = getenv("FID_GEMM_PC") != nullptr || (fg6 && atoi(fg6) == 6);
-    if (bk == 64) {
-        for (int gen = 1; gen <= 2; gen++) {
-            add(gen, 128, 128, 4); add(gen, 128, 64, 4); add(gen, 64, 64, 4);
-        }
-        add(2, 128, 128, 3); add(2, 128, 64, 3); add(2, 64, 64, 3);
-        add(2, 128, 128, 5); add(2, 128, 64, 5); add(2, 64, 64, 5);   // ns = 5: 4 slots + fragment prefetch across K-steps
-        if (gemm_pc) { add(6, 128, 128, 4); add(6, 128, 64, 4); add(6, 64, 64, 4); add(6, 128, 64, 3); add(6, 64, 64, 3); }
-    } else {
-        for (int gen = 1; gen <= 2; gen++) {
-            add(gen, 128, 128, 4); add(gen, 128, 96, 4); add(gen, 128, 64, 4); add(gen, 128, 32, 4);
-        }
-        if (gemm_pc) { add(6, 128, 128, 4); add(6, 128, 96, 4); add(6, 128, 64, 4); }
-    }
+    for (const GemmTile &t : GEMM_TILES)
+        if (t.bk == bk && (t.gen != 6 || gemm_pc)) add(t.gen, t.bm, t.bn, t.ns);
     if (out.empty()) out.push_back(conv_plan(a, num_cus, false));
     for (auto &p : out) p.partial_bytes = p.ksplit > 1 ? (size_t)p.ksplit * a.M * a.Cout_p * 4 : 0;
     return out;
 }
 
-int plan_alt_kind(const ConvPlan &plan) {
-    static const bool pc2_packed = getenv("FID_PC2_PLAIN") == nullptr;
-    if (plan.gen == 8) return pc2_packed ? 1 : 0;
-    if (plan.gen == 9 || plan.gen == 10 || (plan.gen == 12 && plan.ns == 10)) return 2;
-    if (plan.gen == 11) return 3;
-    return 0;
+std::vector<ConvPlan> conv_candidates(const ConvArgs &a, int num_cus, bool allow_split) {
+    std::vector<ConvPlan> all = conv_candidates_all(a, num_cus, allow_split);
+    if (!a.in2) return all;
+    std::vector<ConvPlan> only;                      // fused shortcut (extra K-steps on a second tensor): the LDS-DMA implicit GEMM ...
+    for (const ConvPlan &c : all)
+        if (c.gen == 2 && a.Cin2_p % c.bk == 0) only.push_back(c);
+    if (conv_s2_applicable(a)) only.push_back(patch_plan(10, 128, a.Cout_p, 10));   // ... and the parity-plane stride-2 kernel with the shortcut as one more step per item
+    return only;
 }
 
-// The fraction of the chip's CUs a candidate's launch occupies (1 = all of them, or a family whose grid is not modelled here).  The
-// autotuner can weigh it in (FID_TUNE_SHARE, net.hip): with two batches in flight on two streams a launch that holds half the CUs
-// for the same time leaves the other half to the other lane.
-float conv_plan_cu_share(const ConvArgs &a, const ConvPlan &plan, int num_cus) {
-    long long wgs = -1;
-    if (plan.gen == 1 || plan.gen == 2 || plan.gen == 11) wgs = (long long)cdiv(a.M, plan.bm) * cdiv(a.Cout_p, plan.bn) * std::max(1, plan.ksplit);
-    else if (plan.gen == 9 && plan.ns == 6) wgs = plan.bm >= 512 ? std::min(cdiv(conv_ks_items(a), 2), num_cus / 2) : conv_ks_items(a);
-    else if (plan.gen == 9 && plan.ns == 7) wgs = conv_ks_items(a, true);
-    else if (plan.gen == 9 && plan.ns != 1 && plan.ns != 9) {
-        const long long tiles = plan.ns == 8 ? (long long)cdiv((a.M / (a.Ho * a.Wo)) * a.Wo, 16) * cdiv(a.Ho, 16)
-                                             : (long long)(a.M / (a.Ho * a.Wo)) * cdiv(a.Ho, 14) * cdiv(a.Wo, 14);      // (14 / 16-row tiles: the smaller count)
-        wgs = cdiv((int)tiles, plan.bm / 256) * cdiv(a.Cout_p, plan.bn);
-    }
-    if (wgs < 0 || wgs >= num_cus) return 1.f;
-    return (float)wgs / (float)num_cus;
-}
+namespace {
 
-int conv_launch(fid_ctx *ctx, ConvArgs a, const ConvPlan &plan) {
-    if (plan.gen == 0) return conv_direct_launch(ctx, a);
-    if (plan.gen == 3) return conv_chunked_launch(ctx, a, plan.bn);
-    if (plan.gen == 4) return conv_pp_launch(ctx, a, plan.bn);
-    if (plan.gen == 5) return conv_pc_launch(ctx, a, plan.bn, plan.ns);
-    if (plan.gen == 7) return conv_pcr_launch(ctx, a);
-    if (plan.gen == 8) return conv_pc2_launch(ctx, a);
-    if (plan.gen == 10) return conv_s2_launch(ctx, a);
-    if (plan.gen == 11) return conv_gw_launch(ctx, a, plan.bm, plan.bn);
-    if (plan.gen == 9 && plan.ns == 6) return conv_ks_launch(ctx, a, plan.bm / 256);
-    if (plan.gen == 9 && plan.ns == 7) return conv_ks_launch(ctx, a, 1, true);
-    if (plan.gen == 9 && (plan.ns == 8 || plan.ns == 9)) return conv_wr_launch(ctx, a, plan.bm / 256, plan.bn, plan.ns == 9, 2, true);
-    if (plan.gen == 9) return conv_wr_launch(ctx, a, plan.bm / 256, plan.bn, plan.ns == 1, plan.ns == 4 ? 4 : 2);
+// generations 1, 2 and 6: fills the derived fields (taps, K-steps, split-K plan, tiles) and launches the tile's instance
+int gemm_launch(fid_ctx *ctx, ConvArgs a, const ConvPlan &plan, int gen, int ns) {
     a.T = a.kh * a.kw;
     FID_REQUIRE(a.T >= 1 && a.T <= 25, "conv: %dx%d taps unsupported", a.kh, a.kw);
     FID_REQUIRE(a.Cin_p % 8 == 0 && a.Cout_p % 4 == 0, "conv: channel padding (Cin_p=%d Cout_p=%d)", a.Cin_p, a.Cout_p);
@@ -995,7 +943,7 @@ int conv_launch(fid_ctx *ctx, ConvArgs a, const ConvPlan &plan) {
     a.nchunk = a.Cin_p / plan.bk;
     a.ksteps = cdiv(a.T * a.Cin_p, plan.bk);
     if (a.in2) {                                                // fused shortcut: T2 more taps on the second tensor (generation 2 only)
-        FID_REQUIRE(plan.gen == 2, "conv: the fused shortcut runs on generation 2 only (plan names %d)", plan.gen);
+        FID_REQUIRE(gen == 2, "conv: the fused shortcut runs on generation 2 only (plan names %d)", gen);
         FID_REQUIRE(a.T2 >= 1 && a.T + a.T2 <= 32 && a.kw2 >= 1 && a.s2 >= 1 && a.Cin2_p % plan.bk == 0 && a.in2_bytes <= OOB,
                     "conv: fused shortcut with %d taps of %d channels (BK = %d)", a.T2, a.Cin2_p, plan.bk);
         a.nchunk2 = a.Cin2_p / plan.bk;
@@ -1008,58 +956,110 @@ int conv_launch(fid_ctx *ctx, ConvArgs a, const ConvPlan &plan) {
     a.tiles_m = cdiv(a.M, plan.bm);
     a.tiles_n = cdiv(a.Cout_p, plan.bn);
     FID_REQUIRE(a.ksplit == 1 || a.partial, "conv: split-K without a partial buffer");
-    int rc = FID_E_INVALID;
-    if (plan.gen == 6) {
-        const int key = (plan.bm * 1000 + plan.bn) * 1000 + plan.bk * 10 + plan.ns;
-        switch (key) {
-            case 128128644: rc = launch_pcg<128, 128, 64, 4, 2, 2>(ctx, a); break;
-            case 128064644: rc = launch_pcg<128, 64, 64, 4, 2, 2>(ctx, a); break;
-            case 128064643: rc = launch_pcg<128, 64, 64, 3, 2, 2>(ctx, a); break;
-            case 64064644: rc = launch_pcg<64, 64, 64, 4, 2, 2>(ctx, a); break;
-            case 64064643: rc = launch_pcg<64, 64, 64, 3, 2, 2>(ctx, a); break;
-            case 128128324: rc = launch_pcg<128, 128, 32, 4, 2, 2>(ctx, a); break;
-            case 128096324: rc = launch_pcg<128, 96, 32, 4, 2, 2>(ctx, a); break;
-            case 128064324: rc = launch_pcg<128, 64, 32, 4, 2, 2>(ctx, a); break;
-            default: set_error("conv: no producer/consumer GEMM kernel for tile %dx%dx%d ns=%d", plan.bm, plan.bn, plan.bk, plan.ns); return FID_E_INVALID;
-        }
-    } else if (plan.gen == 2) {
-        const int key = (plan.bm * 1000 + plan.bn) * 1000 + plan.bk * 10 + plan.ns;
-        switch (key) {
-            case 128128644: rc = launch_dma<128, 128, 64, 4, 2, 2>(ctx, a); break;
-            case 128128643: rc = launch_dma<128, 128, 64, 3, 2, 2>(ctx, a); break;
-            case 128128645: rc = launch_dma<128, 128, 64, 4, 2, 2, true>(ctx, a); break;
-            case 128064645: rc = launch_dma<128, 64, 64, 4, 2, 2, true>(ctx, a); break;
-            case 64064645: rc = launch_dma<64, 64, 64, 4, 2, 2, true>(ctx, a); break;
-            case 128064644: rc = launch_dma<128, 64, 64, 4, 2, 2>(ctx, a); break;
-            case 128064643: rc = launch_dma<128, 64, 64, 3, 2, 2>(ctx, a); break;
-            case 64064644: rc = launch_dma<64, 64, 64, 4, 2, 2>(ctx, a); break;
-            case 64064643: rc = launch_dma<64, 64, 64, 3, 2, 2>(ctx, a); break;
-            case 128128324: rc = launch_dma<128, 128, 32, 4, 2, 2>(ctx, a); break;
-            case 128096324: rc = launch_dma<128, 96, 32, 4, 2, 2>(ctx, a); break;
-            case 128064324: rc = launch_dma<128, 64, 32, 4, 2, 2>(ctx, a); break;
-            case 128032324: rc = launch_dma<128, 32, 32, 4, 4, 1>(ctx, a); break;
-            default: set_error("conv: no DMA kernel for tile %dx%dx%d ns=%d", plan.bm, plan.bn, plan.bk, plan.ns); return FID_E_INVALID;
-        }
-    } else {
-        const int key = plan.bm * 1000000 + plan.bn * 1000 + plan.bk;
-        switch (key) {
-            case 128128064: rc = launch_cfg<128, 128, 64, 2, 2>(ctx, a); break;
-            case 128064064: rc = launch_cfg<128, 64, 64, 2, 2>(ctx, a); break;
-            case 64064064: rc = launch_cfg<64, 64, 64, 2, 2>(ctx, a); break;
-            case 128128032: rc = launch_cfg<128, 128, 32, 2, 2>(ctx, a); break;
-            case 128096032: rc = launch_cfg<128, 96, 32, 2, 2>(ctx, a); break;
-            case 128064032: rc = launch_cfg<128, 64, 32, 2, 2>(ctx, a); break;
-            case 128032032: rc = launch_cfg<128, 32, 32, 4, 1>(ctx, a); break;
-            default: set_error("conv: no kernel for tile %dx%dx%d", plan.bm, plan.bn, plan.bk); return FID_E_INVALID;
-        }
-    }
-    FID_TRY(rc);
+    const GemmTile *t = gemm_tile(gen, plan.bm, plan.bn, plan.bk, ns);
+    FID_REQUIRE(t, "conv: no generation-%d implicit-GEMM kernel for tile %dx%dx%d ns=%d", gen, plan.bm, plan.bn, plan.bk, ns);
+    FID_TRY(t->launch(ctx, a));
     if (a.ksplit > 1) {
         const long long n = (long long)a.M * (a.Cout_p / 4);
         hipLaunchKernelGGL(splitk_epilogue, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, ctx->stream, a);
     }
     FID_HIP(hipGetLastError());
     return FID_OK;
+}
+
+// ---- workgroups of a launch, for conv_plan_cu_share (a family without one is not modelled: share 1) ----
+long long wgs_gemm(const ConvArgs &a, const ConvPlan &p, int) { return (long long)cdiv(a.M, p.bm) * cdiv(a.Cout_p, p.bn) * std::max(1, p.ksplit); }
+long long wgs_ks(const ConvArgs &a, const ConvPlan &, int) { return conv_ks_items(a); }
+long long wgs_ks_2perwg(const ConvArgs &a, const ConvPlan &, int num_cus) { return std::min(cdiv(conv_ks_items(a), 2), num_cus / 2); }
+long long wgs_ks_strip(const ConvArgs &a, const ConvPlan &, int) { return conv_ks_items(a, true); }
+long long wgs_tiles(long long tiles, const ConvArgs &a, const ConvPlan &p) { return cdiv((int)tiles, p.bm / 256) * cdiv(a.Cout_p, p.bn); }
+long long wgs_wr(const ConvArgs &a, const ConvPlan &p, int) { return wgs_tiles((long long)(a.M / (a.Ho * a.Wo)) * cdiv(a.Ho, 14) * cdiv(a.Wo, 14), a, p); }   // (14 / 16-row tiles: the smaller count)
+long long wgs_wr_strip(const ConvArgs &a, const ConvPlan &p, int) { return wgs_tiles((long long)cdiv((a.M / (a.Ho * a.Wo)) * a.Wo, 16) * cdiv(a.Ho, 16), a, p); }
+
+// The variant table: every kernel variant the library can launch, and the ONLY place that says which plan tuple names which.  First match wins.
+constexpr int ANY = -1;      // ConvVariant::ns
+#define LAUNCH [](fid_ctx *ctx, const ConvArgs &a, const ConvPlan &p) -> int
+const ConvVariant VARIANTS[] = {
+    // name                 gen  ns  bm   bn  alt rev    force base  launch                                                                       workgroups
+    {"direct",               0, ANY,   0,   0, 0, false, -1, -1, LAUNCH { return conv_direct_launch(ctx, a); }, nullptr},
+    {"gemm.rs",              1, ANY,   0,   0, 0, false, -1, -1, LAUNCH { return gemm_launch(ctx, a, p, 1, 4); }, wgs_gemm},                  // register-staged double buffer
+    {"gemm.dma.ring3",       2,   3,   0,   0, 0, false,  3, -1, LAUNCH { return gemm_launch(ctx, a, p, 2, 3); }, wgs_gemm},                  // LDS-DMA ring, three slots
+    {"gemm.dma",             2,   4,   0,   0, 0, false,  4, -1, LAUNCH { return gemm_launch(ctx, a, p, 2, 4); }, wgs_gemm},                  // ... four slots
+    {"gemm.dma.pf",          2,   5,   0,   0, 0, false,  5, -1, LAUNCH { return gemm_launch(ctx, a, p, 2, 5); }, wgs_gemm},                  // ... four slots + fragment prefetch
+    {"chunked",              3, ANY,   0,   0, 0, false, -1, -1, LAUNCH { return conv_chunked_launch(ctx, a, p.bn); }, nullptr},
+    {"pp",                   4, ANY,   0,   0, 0, false, -1, -1, LAUNCH { return conv_pp_launch(ctx, a, p.bn); }, nullptr},
+    {"pc",                   5,   0,   0,   0, 0, false,  0, -1, LAUNCH { return conv_pc_launch(ctx, a, p.bn, 0); }, nullptr},                // patches two steps ahead
+    {"pc.wahead",            5,   1,   0,   0, 0, false,  1, -1, LAUNCH { return conv_pc_launch(ctx, a, p.bn, 1); }, nullptr},                // weights two steps ahead
+    {"gemm.pc",              6, ANY,   0,   0, 0, false, -1, -1, LAUNCH { return gemm_launch(ctx, a, p, 6, p.ns); }, nullptr},                // LDS-DMA ring with producer waves (3 | 4 slots)
+    {"pcr",                  7, ANY,   0,   0, 0, false, -1, -1, LAUNCH { return conv_pcr_launch(ctx, a); }, nullptr},
+    {"pc2",                  8, ANY,   0,   0, 1, false, -1, -1, LAUNCH { return conv_pc2_launch(ctx, a); }, nullptr},
+    // conv3x3_wr: one tile x 64 couts / a pair of tiles x 128 couts per item; the layer's weights resident; the patches three steps ahead
+    {"wr.one",               9,   0, 256,   0, 2, true,   1, -1, LAUNCH { return conv_wr_launch(ctx, a, 1, p.bn, 0, 2); }, wgs_wr},
+    {"wr.pair",              9,   0, 512,   0, 2, true,   2, -1, LAUNCH { return conv_wr_launch(ctx, a, 2, p.bn, 0, 2); }, wgs_wr},
+    {"wr.resident",          9,   1,   0,   0, 2, true,   3, -1, LAUNCH { return conv_wr_launch(ctx, a, p.bm / 256, p.bn, 1, 2); }, nullptr},
+    {"wr.ring4",             9,   4,   0,   0, 2, true,   4, -1, LAUNCH { return conv_wr_launch(ctx, a, p.bm / 256, p.bn, 0, 4); }, wgs_wr},
+    // conv_ks: the K axis split over two wave groups, one / two items per workgroup (plan tile 256 / 512); on x-packed STRIP tiles
+    {"ks.2perwg",            9,   6, 512,   0, 2, true,   7, -1, LAUNCH { return conv_ks_launch(ctx, a, 2); }, wgs_ks_2perwg},
+    {"ks",                   9,   6,   0,   0, 2, true,   6, -1, LAUNCH { return conv_ks_launch(ctx, a, p.bm / 256); }, wgs_ks},
+    {"ks.strip",             9,   7,   0,   0, 2, true,   8, -1, LAUNCH { return conv_ks_launch(ctx, a, 1, true); }, wgs_ks_strip},
+    // conv3x3_wr on STRIP tiles: a pair x 128 couts / one tile x 128 couts (eight waves) / one tile x 64 couts; the layer's weights resident
+    {"wr.strip.pair",        9,   8, 512,   0, 2, true,  29, -1, LAUNCH { return conv_wr_launch(ctx, a, 2, p.bn, 0, 2, true); }, wgs_wr_strip},
+    {"wr.strip.one128",      9,   8, 256, 128, 2, true,  39, -1, LAUNCH { return conv_wr_launch(ctx, a, 1, p.bn, 0, 2, true); }, wgs_wr_strip},
+    {"wr.strip.one",         9,   8,   0,   0, 2, true,   9, -1, LAUNCH { return conv_wr_launch(ctx, a, p.bm / 256, p.bn, 0, 2, true); }, wgs_wr_strip},
+    {"wr.strip.resident",    9,   9,   0,   0, 2, true,  10, -1, LAUNCH { return conv_wr_launch(ctx, a, p.bm / 256, p.bn, 1, 2, true); }, nullptr},
+    {"s2.sc",               10,  10,   0,   0, 2, false, -1, -1, LAUNCH { return conv_s2_launch(ctx, a); }, nullptr},                          // conv3x3_s2 with a block's shortcut as one more step per item
+    {"s2",                  10, ANY,   0,   0, 2, false, -1, -1, LAUNCH { return conv_s2_launch(ctx, a); }, nullptr},
+    {"gw",                  11, ANY,   0,   0, 3, false, -1, -1, LAUNCH { return conv_gw_launch(ctx, a, p.bm, p.bn); }, wgs_gemm},
+    // a block's shortcut conv fused into the conv that adds it: the executor launches generation `base`, same ns, on the fused argument block
+    {"sc.gemm.ring3",       12,   3,   0,   0, 0, false,  3,  2, nullptr, nullptr},
+    {"sc.gemm",             12,   4,   0,   0, 0, false,  4,  2, nullptr, nullptr},
+    {"sc.gemm.pf",          12,   5,   0,   0, 0, false,  5,  2, nullptr, nullptr},
+    {"sc.s2",               12,  10,   0,   0, 2, false, 10, 10, nullptr, nullptr},
+};
+#undef LAUNCH
+
+}  // namespace
+
+const ConvVariant *conv_variant(const ConvPlan &plan) {
+    for (const ConvVariant &v : VARIANTS)
+        if (v.gen == plan.gen && (v.ns == ANY || v.ns == plan.ns) && (!v.bm || v.bm == plan.bm) && (!v.bn || v.bn == plan.bn)) return &v;
+    return nullptr;
+}
+ConvPlan conv_fused_plan(ConvPlan base) {
+    const ConvPlan plain = base;
+    base.gen = -1;      // (no fused form: names nothing)
+    for (const ConvVariant &v : VARIANTS)
+        if (v.base == plain.gen && v.ns == plain.ns) base.gen = v.gen;
+    return base;
+}
+ConvPlan conv_base_plan(ConvPlan fused) { const ConvVariant *v = conv_variant(fused); fused.gen = v ? v->base : -1; return fused; }
+bool conv_force_match(const ConvPlan &plan, int force_gen, int force_ns) {
+    const ConvVariant *v = conv_variant(plan);
+    return v && (force_gen < 0 || v->gen == force_gen) && (force_ns < 0 || v->force_ns == force_ns);
+}
+
+ConvPlan conv_plan_untuned(const ConvArgs &a, int num_cus, bool allow_split) { return conv_direct_applicable(a) ? patch_plan(0, 0, 0) : conv_plan(a, num_cus, allow_split); }
+
+int plan_alt_kind(const ConvPlan &plan) {
+    static const bool pc2_plain = getenv("FID_PC2_PLAIN") != nullptr;       // experiments: conv_pc2 on the plain weight image
+    const ConvVariant *v = conv_variant(plan);
+    return !v || (v->alt == 1 && pc2_plain) ? 0 : v->alt;
+}
+
+// The fraction of the chip's CUs a candidate's launch occupies (1 = all of them, or a family whose grid is not modelled here).  The
+// autotuner can weigh it in (FID_TUNE_SHARE, net.hip): with two batches in flight on two streams a launch that holds half the CUs
+// for the same time leaves the other half to the other lane.
+float conv_plan_cu_share(const ConvArgs &a, const ConvPlan &plan, int num_cus) {
+    const ConvVariant *v = conv_variant(plan);
+    const long long wgs = v && v->wgs ? v->wgs(a, plan, num_cus) : -1;
+    if (wgs < 0 || wgs >= num_cus) return 1.f;
+    return (float)wgs / (float)num_cus;
+}
+
+int conv_launch(fid_ctx *ctx, ConvArgs a, const ConvPlan &plan) {
+    const ConvVariant *v = conv_variant(plan);
+    FID_REQUIRE(v && v->launch, "conv: plan gen %d ns %d tile %dx%d names no kernel that launches on one argument block", plan.gen, plan.ns, plan.bm, plan.bn);
+    return v->launch(ctx, a, plan);
 }
 
 }  // namespace fid

@@ -60,8 +60,8 @@ enum : int {
     W_X_SRC2 = 23, W_X_T2 = 24, W_X_KW2 = 25, W_X_S2 = 28,
     // ... both forms are in the table: the shortcut conv stays an op of its own (its word 29 = index + 1 of the conv that can absorb it) and the
     // absorbing conv carries a SECOND weight image with rows [kh*kw * Cin_p | taps * Cin2_p] (word 29), the summed bias row (word 30) and the
-    // shortcut's op index + 1 (word 31).  The autotuner decides per batch size: a generation-12 pick = generation 2 on the second image with the
-    // shortcut as extra K-steps (the shortcut op is then skipped), any other pick = the plain conv + the shortcut op.
+    // shortcut's op index + 1 (word 31).  The autotuner decides per batch size: a fused-shortcut pick (the `sc.*` variants of conv.hip's table) = the base kernel on the second
+    // image with the shortcut as extra K-steps (the shortcut op is then skipped), any other pick = the plain conv + the shortcut op.
     W_X_W2OFF = 29, W_X_B2OFF = 30, W_X_SCOP = 31,
 };
 

@@ -546,7 +546,7 @@ int run_op(fid_ctx *ctx, fid_net *net, int oi, const uint8_t *images, int first,
             if (op[W_X_SRC2] == 0 && op[W_X_W2OFF] > 0) {        // a block's shortcut conv that its consumer may absorb (lower.py): word 29 = that conv's op index + 1
                 const int cons = op[W_X_W2OFF] - 1;
                 auto itc = net->tuned[cons].find(batch);
-                if (itc != net->tuned[cons].end() && itc->second.gen == 12 && net->plan_ok[cons].count(batch)) break;   // absorbed at this batch size: nothing to do
+                if (itc != net->tuned[cons].end() && conv_fuses_shortcut(itc->second) && net->plan_ok[cons].count(batch)) break;   // absorbed at this batch size: nothing to do
             }
             const TensorView src = view(net, op[W_SRC], first);
             ConvArgs a{}, af{};
@@ -581,7 +581,7 @@ int run_op(fid_ctx *ctx, fid_net *net, int oi, const uint8_t *images, int first,
                             (dst.H - 1) * op[W_X_S2] + (op[W_X_T2] / op[W_X_KW2] - 1) < x2.H && (dst.W - 1) * op[W_X_S2] + op[W_X_KW2] - 1 < x2.W,
                             "op %d: bad fused shortcut-conv record", oi);
                 FID_REQUIRE(op[W_X_W2OFF] > 0 && op[W_X_B2OFF] > 0 && op[W_X_SCOP] > 0 && op[W_X_SCOP] <= oi && op[W_RES] >= 0, "op %d: fused shortcut-conv record without its second image", oi);
-                // the fused form (a generation-12 pick): second weight image [kh*kw * Cin_p | T2 * Cin2_p], summed bias, no residual
+                // the fused form (a fused-shortcut pick): second weight image [kh*kw * Cin_p | T2 * Cin2_p], summed bias, no residual
                 af = a;
                 af.in2 = x2.ptr; af.H2 = x2.H; af.W2 = x2.W; af.Cin2_p = x2.Cp; af.T2 = op[W_X_T2]; af.kw2 = op[W_X_KW2]; af.s2 = op[W_X_S2];
                 af.in2_bytes = (unsigned)((size_t)batch * x2.H * x2.W * x2.Cp * 2);
@@ -593,20 +593,18 @@ int run_op(fid_ctx *ctx, fid_net *net, int oi, const uint8_t *images, int first,
             }
             a.partial = af.partial = (float *)partial_ws;
             a.rev = af.rev = net->alternate && op[W_SRC] >= 0 && !net->tdir[op[W_SRC]];
-            // every candidate of this op: the plain conv's, and (generation 12) generation 2's with the shortcut as extra K-steps
+            // every candidate of this op: the plain conv's, and the fused argument block's as fused-shortcut picks
             auto all_candidates = [&]() {
                 std::vector<ConvPlan> v = conv_candidates(a, ctx->num_cus, true);
                 static const bool no_sc = getenv("FID_NO_SC_RUNTIME") != nullptr;
                 if (has_sc && !no_sc)
-                    for (ConvPlan c : conv_candidates(af, ctx->num_cus, true)) { c.gen = 12; v.push_back(c); }   // (ns = 10: conv3x3_s2's form, else generation 2's)
+                    for (const ConvPlan &c : conv_candidates(af, ctx->num_cus, true)) v.push_back(conv_fused_plan(c));
                 return v;
             };
             auto launch_plan = [&](const ConvPlan &c) -> int {
-                if (c.gen != 12) return conv_launch(ctx, a, c);
-                ConvPlan c2 = c;
-                c2.gen = c.ns == 10 ? 10 : 2;
+                if (!conv_fuses_shortcut(c)) return conv_launch(ctx, a, c);
                 af.w_alt = a.w_alt;                              // (the 3x3 part in fragment order: set_alt_weights built it from the plain first image)
-                return conv_launch(ctx, af, c2);
+                return conv_launch(ctx, af, conv_base_plan(c));
             };
             ConvPlan plan;
             auto &cache = net->tuned[oi];
@@ -632,18 +630,14 @@ int run_op(fid_ctx *ctx, fid_net *net, int oi, const uint8_t *images, int first,
                 // operands (the op is idempotent) and keep the fastest; a split-K plan must win by 10 %
                 // to be preferred (its summation order differs from the unsplit kernels)
                 std::vector<ConvPlan> cands = all_candidates();
-                if (const char *fg = getenv("FID_FORCE_GEN")) {      // tests: exercise one kernel family wherever it applies
+                // tests: exercise one kernel family (FID_FORCE_GEN) / one variant of it (FID_FORCE_NS) wherever it applies
+                auto keep_forced = [&](int force_gen, int force_ns) {
                     std::vector<ConvPlan> only;
-                    for (const ConvPlan &c : cands)
-                        if (c.gen == atoi(fg)) only.push_back(c);
+                    for (const ConvPlan &c : cands) if (conv_force_match(c, force_gen, force_ns)) only.push_back(c);
                     if (!only.empty()) cands = only;
-                }
-                if (const char *fn = getenv("FID_FORCE_NS")) {       // tests: one ring variant of generation 2 / 5
-                    std::vector<ConvPlan> only;
-                    for (const ConvPlan &c : cands)
-                        if (((c.gen == 2 || c.gen == 5 || c.gen == 12) && c.ns == atoi(fn)) || (c.gen == 9 && (c.ns == 1 ? 3 : (c.ns == 4 ? 4 : (c.ns == 6 ? (c.bm == 512 ? 7 : 6) : (c.ns >= 7 ? c.ns + 1 + (c.ns == 8 && c.bm == 512 ? 20 : 0) + (c.ns == 8 && c.bm == 256 && c.bn == 128 ? 30 : 0) : c.bm / 256)))) == atoi(fn))) only.push_back(c);
-                    if (!only.empty()) cands = only;
-                }
+                };
+                if (const char *fg = getenv("FID_FORCE_GEN")) keep_forced(atoi(fg), -1);
+                if (const char *fn = getenv("FID_FORCE_NS")) keep_forced(-1, atoi(fn));
                 const float pc2_bias = getenv("FID_PC2_BIAS") ? (float)atof(getenv("FID_PC2_BIAS")) : 1.f;
                 hipEvent_t e0, e1;
                 FID_HIP(hipEventCreate(&e0));
@@ -700,16 +694,16 @@ int run_op(fid_ctx *ctx, fid_net *net, int oi, const uint8_t *images, int first,
                         if (rep > 0) tmin = std::min(tmin, ms);
                     }
                     float score = c.ksplit > 1 ? tmin * 1.1f : tmin;
-                    if (has_sc && c.gen != 12) score += t_sc;
+                    if (has_sc && !conv_fuses_shortcut(c)) score += t_sc;
                     // FID_TUNE_SHARE = s (0 .. 1; plans for two-lane deployments, tools/make_plan.sh): a launch on a fraction f of the CUs scores
                     // t (1 - s (1 - f)) -- the CUs it leaves free run the other lane's kernels.  Measured on IResNet's 7x7 layers at 64 faces:
-                    // conv_ks MOSAIC (128 workgroups, 38 us) against generation 2 (392 workgroups, 36 us): the step is 1.3 % shorter with MOSAIC.
+                    // conv_ks MOSAIC (128 workgroups, 38 us) against the LDS-DMA implicit GEMM (392 workgroups, 36 us): the step is 1.3 % shorter with MOSAIC.
                     static const float tune_share = getenv("FID_TUNE_SHARE") ? (float)atof(getenv("FID_TUNE_SHARE")) : 0.f;
                     if (tune_share > 0.f) score *= 1.f - tune_share * (1.f - conv_plan_cu_share(a, c, ctx->num_cus));
-                    if (c.gen == 8) score *= pc2_bias;          // experiments: FID_PC2_BIAS < 1 prefers the two-tile kernel although it is slower alone
+                    if (pc2_bias != 1.f && !strcmp(conv_plan_name(c), "pc2")) score *= pc2_bias;          // experiments: FID_PC2_BIAS < 1 prefers the two-tile kernel although it is slower alone
                     static const int tune_verbose = getenv("FID_TUNE_LOG") ? atoi(getenv("FID_TUNE_LOG")) : 0;
                     if (tune_verbose >= 2)
-                        fprintf(stderr, "[cand] op %d gen %d tile %dx%dx%d ns %d split %d: %.1f us\n", oi, c.gen, c.bm, c.bn, c.bk, c.ns, c.ksplit, tmin * 1e3f);
+                        fprintf(stderr, "[cand] op %d gen %d tile %dx%dx%d ns %d split %d: %.1f us %s\n", oi, c.gen, c.bm, c.bn, c.bk, c.ns, c.ksplit, tmin * 1e3f, conv_plan_name(c));
                     if (score < best) { best = score; plan = c; }
                 }
                 (void)hipEventDestroy(e0);
@@ -726,11 +720,10 @@ int run_op(fid_ctx *ctx, fid_net *net, int oi, const uint8_t *images, int first,
                     }
                 }
                 if (getenv("FID_TUNE_LOG"))
-                    fprintf(stderr, "[tune] op %d M=%d Cin_p=%d Cout_p=%d k=%d s=%d -> gen %d tile %dx%dx%d ns %d split %d (%.1f us)\n", oi, a.M,
-                            a.Cin_p, a.Cout_p, a.kh, a.stride, plan.gen, plan.bm, plan.bn, plan.bk, plan.ns, plan.ksplit, best * 1e3f);
+                    fprintf(stderr, "[tune] op %d M=%d Cin_p=%d Cout_p=%d k=%d s=%d -> gen %d tile %dx%dx%d ns %d split %d (%.1f us) %s\n", oi, a.M,
+                            a.Cin_p, a.Cout_p, a.kh, a.stride, plan.gen, plan.bm, plan.bn, plan.bk, plan.ns, plan.ksplit, best * 1e3f, conv_plan_name(plan));
             } else {
-                plan = conv_direct_applicable(a) ? ConvPlan{} : conv_plan(a, ctx->num_cus, partial_ws != nullptr);
-                if (conv_direct_applicable(a)) { plan.gen = 0; plan.ksplit = 1; }
+                plan = conv_plan_untuned(a, ctx->num_cus, partial_ws != nullptr);
             }
             FID_TRY(set_alt_weights(ctx, net, oi, a, plan));
             FID_TRY(launch_plan(plan));

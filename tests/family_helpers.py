@@ -1,5 +1,5 @@
-"""Shared pieces of the kernel-family GPU tests (test_gpu_conv_families.py, test_gpu_batch_shapes.py): the layer stacks, the translation of a
-test's generation code into the autotuner hooks FID_FORCE_GEN / FID_FORCE_NS, the check of WHICH family ran, and the activation-slot guard
+"""Shared pieces of the kernel-family GPU tests (test_gpu_conv_families.py, test_gpu_batch_shapes.py): the layer stacks, the table that
+turns a test's family code into the autotuner hooks FID_FORCE_GEN / FID_FORCE_NS and into the check of WHICH family ran, and the activation-slot guard
 (poison the rows at or beyond the batch of a net that runs below its max_batch, check them afterwards).  Plain module, no fixtures; the slot
 arithmetic is pure Python on lower()'s tensor table, so tests/test_slot_guard_cpu.py checks it without a GPU."""
 import numpy as np
@@ -12,48 +12,55 @@ from scrfd_arcface_facerecognition_amd.lower import OP_CONV, OP_LATFPN, OP_STEMB
 W_TYPE, W_DST, W_X_DST2, W_L_LAT, W_S_DST2, W_X_SRC2, W_X_W2OFF, T_SLOT = 0, 2, 20, 22, 24, 23, 29, 5
 
 
+def _row(name, tup, env, **match):
+    return {"name": name, "tuple": tup, "env": {"FID_" + k: str(v) for k, v in env.items()}, "match": match}
+
+
+# The tests' own decode of a family code, once: the library's name of the variant and one plan tuple (gen bm bn bk ksplit ns) of it (tests/
+# test_conv_variants_cpu.py checks both against the library), the autotuner hooks that force it, and the fields of a plans() row that say it ran.
+# 59 = generation 5 with register-staged producers; 9x: conv3x3_wr and conv_ks; 9xx: conv3x3_wr on STRIP tiles.
+FAMILIES = {
+    0: _row("direct", (0, 0, 0, 0, 1, 0), {"FORCE_GEN": 0}, gen=0),
+    1: _row("gemm.rs", (1, 128, 128, 64, 1, 4), {"FORCE_GEN": 1}, gen=1),
+    2: _row("gemm.dma", (2, 128, 64, 64, 1, 4), {"FORCE_GEN": 2}, gen=2),
+    3: _row("chunked", (3, 256, 64, 32, 1, 0), {"FORCE_GEN": 3}, gen=3),
+    4: _row("pp", (4, 512, 48, 32, 1, 0), {"FORCE_GEN": 4}, gen=4),
+    5: _row("pc", (5, 256, 96, 32, 1, 0), {"FORCE_GEN": 5}, gen=5),
+    6: _row("gemm.pc", (6, 128, 64, 64, 1, 3), {"FORCE_GEN": 6}, gen=6),
+    7: _row("pcr", (7, 256, 64, 32, 1, 0), {"FORCE_GEN": 7}, gen=7),
+    8: _row("pc2", (8, 512, 64, 32, 1, 0), {"FORCE_GEN": 8}, gen=8),
+    10: _row("s2", (10, 128, 96, 32, 1, 0), {"FORCE_GEN": 10}, gen=10),
+    11: _row("gw", (11, 64, 256, 32, 1, 0), {"FORCE_GEN": 11}, gen=11),
+    25: _row("gemm.dma.pf", (2, 64, 64, 64, 1, 5), {"FORCE_GEN": 2, "FORCE_NS": 5}, gen=2, ns=5),
+    51: _row("pc.wahead", (5, 256, 64, 32, 1, 1), {"FORCE_GEN": 5, "FORCE_NS": 1}, gen=5, ns=1),
+    59: _row("pc", (5, 256, 64, 32, 1, 0), {"FORCE_GEN": 5, "PC_RS": 1}, gen=5),
+    91: _row("wr.one", (9, 256, 64, 32, 1, 0), {"FORCE_GEN": 9, "FORCE_NS": 1}, gen=9, ns=0, bm=256),
+    92: _row("wr.pair", (9, 512, 128, 32, 1, 0), {"FORCE_GEN": 9, "FORCE_NS": 2}, gen=9, ns=0, bm=512),
+    93: _row("wr.resident", (9, 256, 128, 32, 1, 1), {"FORCE_GEN": 9, "FORCE_NS": 3}, gen=9, ns=1),
+    94: _row("wr.ring4", (9, 256, 64, 32, 1, 4), {"FORCE_GEN": 9, "FORCE_NS": 4}, gen=9, ns=4),
+    96: _row("ks", (9, 256, 64, 32, 1, 6), {"FORCE_GEN": 9, "FORCE_NS": 6}, gen=9, ns=6, bm=256),
+    97: _row("ks.2perwg", (9, 512, 64, 32, 1, 6), {"FORCE_GEN": 9, "FORCE_NS": 7}, gen=9, ns=6, bm=512),
+    98: _row("ks.strip", (9, 256, 64, 32, 1, 7), {"FORCE_GEN": 9, "FORCE_NS": 8}, gen=9, ns=7),
+    909: _row("wr.strip.one", (9, 256, 64, 32, 1, 8), {"FORCE_GEN": 9, "FORCE_NS": 9}, gen=9, ns=8, bm=256, bn=64),
+    929: _row("wr.strip.pair", (9, 512, 128, 32, 1, 8), {"FORCE_GEN": 9, "FORCE_NS": 29}, gen=9, ns=8, bm=512, bn=128),
+    939: _row("wr.strip.one128", (9, 256, 128, 32, 1, 8), {"FORCE_GEN": 9, "FORCE_NS": 39}, gen=9, ns=8, bm=256, bn=128),
+    910: _row("wr.strip.resident", (9, 256, 256, 32, 1, 9), {"FORCE_GEN": 9, "FORCE_NS": 10}, gen=9, ns=9),
+}
+
+
 def force_family(monkeypatch, code):
-    """a test's generation code -> FID_FORCE_GEN / FID_FORCE_NS (59 = generation 5 with register-staged producers; codes >= 900 and the
-    two-digit ring / tile codes carry the variant in their last digits; every other code is the generation itself)"""
-    if code == 59:
-        monkeypatch.setenv("FID_FORCE_GEN", "5")
-        monkeypatch.setenv("FID_PC_RS", "1")
-    elif code >= 900:
-        monkeypatch.setenv("FID_FORCE_GEN", str(code // 100))
-        monkeypatch.setenv("FID_FORCE_NS", str(code % 100))
-    elif code in (25, 51, 91, 92, 93, 94, 96, 97, 98):
-        monkeypatch.setenv("FID_FORCE_GEN", str(code // 10))
-        monkeypatch.setenv("FID_FORCE_NS", str(code % 10))
-    else:
-        monkeypatch.setenv("FID_FORCE_GEN", str(code))
+    """a test's family code -> the autotuner hooks of its FAMILIES row (and none of another row's)"""
+    for k in ("FID_FORCE_GEN", "FID_FORCE_NS", "FID_PC_RS"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in FAMILIES[code]["env"].items():
+        monkeypatch.setenv(k, v)
 
 
 def forced_ran(cn, code, batch=None):
-    """ops of the net whose pick is the kernel family the test forced (code = the test's generation code: FID_FORCE_GEN, or
-    FID_FORCE_GEN * 10 + FID_FORCE_NS for the ring / tile variants).  FID_FORCE_GEN only restricts the candidates where the family
-    applies; a test that asserted nothing about the pick would pass on another family's result.  batch: only the picks made for that
-    batch size (a net that ran several)."""
-    def hit(p):
-        if code in (25, 51):
-            return p["gen"] == code // 10 and p["ns"] == (5 if code == 25 else 1)
-        if code == 59:
-            return p["gen"] == 5
-        if code in (91, 92):
-            return p["gen"] == 9 and p["ns"] not in (1, 4, 6) and p["bm"] // 256 == code % 10
-        if code == 93:
-            return p["gen"] == 9 and p["ns"] == 1
-        if code == 94:
-            return p["gen"] == 9 and p["ns"] == 4
-        if code in (96, 97):                                    # conv_ks: one / two items per workgroup (plan tile 256 / 512)
-            return p["gen"] == 9 and p["ns"] == 6 and p["bm"] == (256 if code == 96 else 512)
-        if code == 98:                                          # conv_ks on x-packed STRIP tiles
-            return p["gen"] == 9 and p["ns"] == 7
-        if code in (909, 929, 939):                             # conv_wr on STRIP tiles: one tile x 64 couts / a pair x 128 couts / one tile x 128 couts
-            return p["gen"] == 9 and p["ns"] == 8 and (p["bm"], p["bn"]) == {909: (256, 64), 929: (512, 128), 939: (256, 128)}[code]
-        if code == 910:                                         # conv_wr on STRIP tiles, the layer's weights resident
-            return p["gen"] == 9 and p["ns"] == 9
-        return p["gen"] == code
-    return [p["name"] for p in cn.plans() if hit(p) and (batch is None or p["batch"] == batch)]
+    """ops of the net whose pick is the kernel variant the test forced (code: a FAMILIES row).  The hooks only restrict the candidates where the variant applies; a test
+    that asserted nothing about the pick would pass on another family's result.  batch: only the picks made for that batch size (a net that ran several)."""
+    match = FAMILIES[code]["match"]
+    return [p["name"] for p in cn.plans() if all(p[k] == v for k, v in match.items()) and (batch is None or p["batch"] == batch)]
 
 
 def stack(hw, chans, res=True):
