@@ -11,19 +11,24 @@ from scrfd_arcface_facerecognition_amd.archs import BN_EPS
 
 
 def _bn(x, P, prefix):
-    g, b = torch.from_numpy(P[prefix + ".gamma"]), torch.from_numpy(P[prefix + ".beta"])
-    m, v = torch.from_numpy(P[prefix + ".mean"]), torch.from_numpy(P[prefix + ".var"])
+    g, b = torch.from_numpy(P[prefix + ".gamma"]).to(x.dtype), torch.from_numpy(P[prefix + ".beta"]).to(x.dtype)
+    m, v = torch.from_numpy(P[prefix + ".mean"]).to(x.dtype), torch.from_numpy(P[prefix + ".var"]).to(x.dtype)
     if x.dim() == 4:
         return F.batch_norm(x, m, v, g, b, False, 0.0, BN_EPS)
     return (x - m) / torch.sqrt(v + BN_EPS) * g + b
 
 
 @torch.no_grad()
-def run_net(net, P, blob, keep=None):
+def run_net(net, P, blob, keep=None, dtype=torch.float32, store=None):
     """blob: float32 [N,3,H,W] (already normalised, RGB).  Returns {name: np.ndarray} for the net
     outputs (plus any tensor named in `keep`).  DetHead outputs are (scores[N,HWA,1],
-    bbox[N,HWA,4], kps[N,HWA,10]) like the 9 ONNX outputs of SCRFD."""
-    t = {"input": torch.from_numpy(np.ascontiguousarray(blob)).float()}
+    bbox[N,HWA,4], kps[N,HWA,10]) like the 9 ONNX outputs of SCRFD.
+    dtype: the precision the net is evaluated in.  store: None, or store(name, y) -> y applied to the result of
+    every conv / maxpool node, the tensors the executor keeps as fp16 (tests/exact_probe.py rounds them there, in
+    float64: the exact reference).  FC and DetHead results are fp32 tensors on the device and do not pass through it."""
+    t = {"input": torch.from_numpy(np.ascontiguousarray(blob)).to(dtype)}
+    par = lambda k: torch.from_numpy(P[k]).to(dtype)
+    stored = (lambda name, y: y) if store is None else store
     for n in net.nodes:
         x = t[n.src]
         if n.kind == "conv":
@@ -32,8 +37,8 @@ def run_net(net, P, blob, keep=None):
                 x = _bn(x, P, w + ".pre_bn")
             if n.pre_avgpool:
                 x = F.avg_pool2d(x, 2, 2)
-            b = torch.from_numpy(P[w + ".bias"]) if n.bias else None
-            y = F.conv2d(x, torch.from_numpy(P[w + ".weight"]), b, n.stride, n.pad, 1, n.groups)
+            b = par(w + ".bias") if n.bias else None
+            y = F.conv2d(x, par(w + ".weight"), b, n.stride, n.pad, 1, n.groups)
             if n.post_bn:
                 y = _bn(y, P, w + ".post_bn")
             if n.res is not None:
@@ -44,29 +49,29 @@ def run_net(net, P, blob, keep=None):
             if n.act == "relu":
                 y = F.relu(y)
             elif n.act == "prelu":
-                y = F.prelu(y, torch.from_numpy(P[w + ".prelu"]))
-            t[n.name] = y
+                y = F.prelu(y, par(w + ".prelu"))
+            t[n.name] = stored(n.name, y)
         elif n.kind == "maxpool":
-            t[n.name] = F.max_pool2d(x, n.k, n.stride, n.pad)
+            t[n.name] = stored(n.name, F.max_pool2d(x, n.k, n.stride, n.pad))
         elif n.kind == "fc":
             w = n.wname
             if n.pre_bn:
                 x = _bn(x, P, w + ".pre_bn")
-            y = x.flatten(1) @ torch.from_numpy(P[w + ".weight"]).T
+            y = x.flatten(1) @ par(w + ".weight").T
             if n.bias:
-                y = y + torch.from_numpy(P[w + ".bias"])
+                y = y + par(w + ".bias")
             if n.post_bn:
                 y = _bn(y, P, w + ".post_bn")
             t[n.name] = y
         elif n.kind == "dethead":
             w, A = n.wname, n.num_anchors
             pad = n.k // 2
-            cls = torch.sigmoid(F.conv2d(x, torch.from_numpy(P[w + ".cls.weight"]),
-                                         torch.from_numpy(P[w + ".cls.bias"]), 1, pad))
-            bb = F.conv2d(x, torch.from_numpy(P[w + ".bbox.weight"]),
-                          torch.from_numpy(P[w + ".bbox.bias"]), 1, pad) * float(P[w + ".bbox.scale"][0])
-            kp = F.conv2d(x, torch.from_numpy(P[w + ".kps.weight"]),
-                          torch.from_numpy(P[w + ".kps.bias"]), 1, pad)
+            cls = torch.sigmoid(F.conv2d(x, par(w + ".cls.weight"),
+                                         par(w + ".cls.bias"), 1, pad))
+            bb = F.conv2d(x, par(w + ".bbox.weight"),
+                          par(w + ".bbox.bias"), 1, pad) * float(P[w + ".bbox.scale"][0])
+            kp = F.conv2d(x, par(w + ".kps.weight"),
+                          par(w + ".kps.bias"), 1, pad)
             N = x.shape[0]
             t[n.name] = (cls.permute(0, 2, 3, 1).reshape(N, -1, 1),
                          bb.permute(0, 2, 3, 1).reshape(N, -1, 4),

@@ -1,0 +1,563 @@
+"""Bit-exact integer probes of the conv kernels (test_exact_probe_cpu.py, test_gpu_conv_exact.py).  Plain module, no fixtures.
+
+When every stored activation, weight, bias and PReLU slope of a layer is a small integer times a power of two, every fp16 x fp16 product and
+every partial sum of its convolution is exactly representable in fp32: the fp32 accumulator then holds the same number whatever the summation
+order, the tile shape, the K split or the MFMA shape, and the stored fp16 value is the round-to-nearest-even of ONE exact number.  A float64
+reference that rounds every node to fp16 states it bit for bit -- for every kernel variant, whichever variant runs the layers in front.
+
+  int_params       such parameters for a Net whose nodes carry no BatchNorm (bias=True, post_bn=False, pre_bn=False)
+  reference        the net in float64, every fp16 tensor rounded with numpy's astype(np.float16) (oracle.nets.run_net(dtype, store))
+  check_exactness  the CONDITIONS under which the comparison may be exact and can see a fault, asserted on the reference alone
+  assert_same_bits the comparator: finite, then equality of the fp16 values (+0 == -0), with positions / bit patterns / ulp histogram on failure
+  PROBES           the probe nets: a 3 -> 64 stem, a 1x1 widening conv where the op needs more channels, then the op under test
+
+BatchNorm is out of scope: gamma / sqrt(var + eps) cannot be made an exact power of two, so the folded forms (IResNet's "ir" block with its
+border-class bias rows, a shortcut conv with BN) stay with the tolerance tests."""
+import functools
+from dataclasses import dataclass, field
+from typing import Dict, List
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from oracle import align, nets as onets
+from scrfd_arcface_facerecognition_amd.archs import Conv, Net
+
+IN_MEAN, IN_SCALE = 127.5, 2.0        # the first conv reads 2 p - 255 with weights W * in_scale / 2 = W (lower.py): exact as well
+PIXELS = (120, 136)                   # |2 p - 255| <= 15
+GUARD = 2.0 ** 22                     # partial sums stay two bits under fp32's 24 (an MFMA may align its addends to the largest exponent)
+F16_MAX = 65504.0
+
+
+# ---- parameters --------------------------------------------------------------------------------------------------------------------------
+
+def int_params(net, seed, layers=None):
+    """{name: float32 array} for every conv node of `net`: weights = signed integers from `mags` at `density`, times 2 ** `exp`; integer biases
+    in +-`bias` times 2 ** `exp`; PReLU slopes from {0.5, 0.25}.  layers: {node name: overrides of density / mags / exp / bias}.  Every value is
+    exactly representable in fp16."""
+    rng = np.random.default_rng(seed)
+    P = {}
+    for n in net.nodes:
+        if n.kind == "dethead":                               # integer weights and biases, bbox.scale = 1: the fp32 bbox / kps channels are exact sums
+            for part, c in (("cls", n.num_anchors), ("bbox", 4 * n.num_anchors), ("kps", 10 * n.num_anchors)):
+                shape = (c, n.cin, n.k, n.k)
+                P[f"{n.wname}.{part}.weight"] = (rng.choice((1, 2), shape) * rng.choice([-1, 1], shape)).astype(np.float32)     # dense: every column reaches each of the few couts' block
+                P[f"{n.wname}.{part}.bias"] = rng.integers(-64, 65, c).astype(np.float32)
+            P[n.wname + ".bbox.scale"] = np.ones(1, np.float32)
+            continue
+        assert n.kind == "conv" and n.bias and not n.post_bn and not n.pre_bn, n.name
+        o = dict(density=1.0 if (n.src == "input" or n.groups > 1) else 1.0 / 3.0, mags=(1,) if n.src == "input" else (1, 2), exp=0, bias=8)
+        o.update((layers or {}).get(n.name, {}))
+        shape = (n.cout, n.cin // n.groups, n.k, n.k)
+        w = rng.choice(o["mags"], shape) * rng.choice([-1, 1], shape) * (rng.random(shape) < o["density"])
+        P[n.wname + ".weight"] = (w * 2.0 ** o["exp"]).astype(np.float32)
+        P[n.wname + ".bias"] = (rng.integers(-o["bias"], o["bias"] + 1, n.cout) * 2.0 ** o["exp"]).astype(np.float32)
+        if n.act == "prelu":
+            P[n.wname + ".prelu"] = rng.choice([0.5, 0.25], n.cout).astype(np.float32)
+    for k, v in P.items():
+        assert np.array_equal(v.astype(np.float16).astype(np.float32), v), k
+    return P
+
+
+def int_images(seed, batch, hw):
+    return np.random.default_rng(seed).integers(PIXELS[0], PIXELS[1], (batch,) + tuple(hw) + (3,), dtype=np.uint8)
+
+
+# ---- the exact reference -----------------------------------------------------------------------------------------------------------------
+
+def _r16(y):
+    """float64 tensor -> its fp16 rounding (nearest even), as float64"""
+    return torch.from_numpy(y.numpy().astype(np.float16).astype(np.float64))
+
+
+def reference(net, P, images, raw=None):
+    """{node name: float64 [B, H, W, C] holding fp16 values} for every conv node.  raw: a dict that receives the values BEFORE the rounding"""
+    out = {}
+
+    def store(name, y):
+        if raw is not None:
+            raw[name] = y.permute(0, 2, 3, 1).numpy().copy()
+        with np.errstate(over="ignore"):
+            r = _r16(y)
+        out[name] = r.permute(0, 2, 3, 1).numpy().copy()
+        return r
+
+    blob = align.blob_from_images(list(images), net.in_scale, net.in_mean)
+    res = onets.run_net(net, P, blob, keep=[n.name for n in net.nodes], dtype=torch.float64, store=store)
+    for n in net.nodes:
+        if n.kind == "dethead":                               # an fp32 tensor on the device: (scores, bbox, kps) as float64, not rounded
+            out[n.name] = res[n.name]
+    out["input"] = np.transpose(blob, (0, 2, 3, 1)).astype(np.float64)
+    return out
+
+
+def _nchw(a):
+    return torch.from_numpy(np.ascontiguousarray(np.transpose(a, (0, 3, 1, 2))))
+
+
+def _chunks(n):
+    """the pieces the K axis of a conv node is summed in: 32-channel chunks (one kernel row each for a depthwise layer), as weight masks"""
+    cin_g = n.cin // n.groups
+    masks = []
+    if n.groups == 1:
+        for c0 in range(0, cin_g, 32):
+            m = torch.zeros(1, cin_g, 1, 1, dtype=torch.bool)
+            m[:, c0:c0 + 32] = True
+            masks.append(m)
+    else:
+        for r in range(n.k):
+            m = torch.zeros(1, 1, n.k, 1, dtype=torch.bool)
+            m[:, :, r] = True
+            masks.append(m)
+    return masks
+
+
+def eval_node(n, ref, P, mode="exact", rounded=True):
+    """One conv node from the reference's STORED inputs, [B, H, W, C] as float64 holding fp16 values.  mode:
+      exact          float64, one conv
+      f32_fwd        float32, the K axis in 32-channel chunks, first to last
+      f32_rev        float32, the chunks last to first, the channels of every chunk flipped
+      fault_tap      the centre tap does not reach pixel (0, 0) of image 0
+      fault_f16acc   the partial sum is rounded to fp16 between the chunks
+      fault_rtz      the store rounds toward zero
+    rounded=False: the float64 value before the store (the f32 modes always return the fp32 accumulator's value)"""
+    dt = torch.float32 if mode.startswith("f32") else torch.float64
+    x = _nchw(ref[n.src]).to(dt)
+    if n.pre_avgpool:
+        x = F.avg_pool2d(x, 2, 2)
+    w = torch.from_numpy(P[n.wname + ".weight"]).to(dt)
+    conv = lambda xx, ww: F.conv2d(xx, ww, None, n.stride, n.pad, 1, n.groups)
+    if mode == "exact" or mode == "fault_rtz":
+        y = conv(x, w)
+    elif mode == "fault_tap":
+        y = conv(x, w)
+        x0 = torch.zeros_like(x)
+        x0[0, :, 0, 0] = x[0, :, 0, 0]
+        w0 = torch.zeros_like(w)
+        w0[:, :, n.k // 2, n.k // 2] = w[:, :, n.k // 2, n.k // 2]
+        y = y - conv(x0, w0)                                  # (that product only reaches output pixel (0, 0) of image 0)
+    else:
+        masks = _chunks(n)
+        if mode == "f32_rev":
+            masks = masks[::-1]
+        y = torch.zeros_like(conv(x, w))
+        for m in masks:
+            if mode == "f32_rev" and n.groups == 1:
+                idx = torch.nonzero(m.flatten()).flatten().flip(0)
+                part = F.conv2d(x[:, idx], w[:, idx], None, n.stride, n.pad)
+            else:
+                part = conv(x, w * m)
+            y = y + part
+            if mode == "fault_f16acc":
+                y = _r16(y)
+    y = y + torch.from_numpy(P[n.wname + ".bias"]).to(dt)[None, :, None, None]
+    if n.res is not None:
+        r = _nchw(ref[n.res]).to(dt)
+        if n.res_up2:
+            r = F.interpolate(r, scale_factor=2, mode="nearest")
+        y = y + r
+    if n.act == "relu":
+        y = F.relu(y)
+    elif n.act == "prelu":
+        y = F.prelu(y, torch.from_numpy(P[n.wname + ".prelu"]).to(dt))
+    y = y.permute(0, 2, 3, 1).numpy()
+    if mode.startswith("f32"):
+        return y                                              # the fp32 accumulator's value, before the store
+    if not rounded:
+        return y
+    h = y.astype(np.float16)
+    if mode == "fault_rtz":
+        away = np.abs(h.astype(np.float64)) > np.abs(y)
+        h = np.where(away, np.nextafter(h, np.float16(0)), h)
+    return h.astype(np.float64)
+
+
+# ---- the conditions ----------------------------------------------------------------------------------------------------------------------
+
+def lsb_of(a):
+    """the largest power of two that divides every entry of `a` (1.0 for an all-zero array)"""
+    a = np.asarray(a, dtype=np.float64)
+    a = a[a != 0]
+    if a.size == 0:
+        return 1.0
+    m, e = np.frexp(np.abs(a))                                # a = m * 2 ** e, 0.5 <= m < 1: m * 2 ** 53 is an integer
+    mi = (m * 2.0 ** 53).astype(np.int64)
+    tz = np.log2((mi & -mi).astype(np.float64))               # trailing zero bits of the integer significand
+    return float(2.0 ** np.min(e - 53 + tz))
+
+
+def _on_grid(a, g):
+    q = np.asarray(a, dtype=np.float64) / g
+    return bool(np.all(q == np.round(q)))
+
+
+def _is_f16(a):
+    with np.errstate(over="ignore"):
+        return np.asarray(a).astype(np.float16).astype(np.float64) == np.asarray(a, dtype=np.float64)
+
+
+def check_exactness(net, P, images, probed, onchip=(), ref=None, raw=None):
+    """Asserts, on the reference alone, that the nodes `probed` of the net may be compared bit for bit and that the comparison has power;
+    `onchip`: the nodes a fused op never stores.  ref / raw: reference()'s results where the caller already has them.  Returns the figures
+    per node ({name: dict})."""
+    if ref is None:
+        raw = {}
+        ref = reference(net, P, images, raw)
+    grid = {"input": 1.0}                                     # 2 p - 255: odd integers
+    stats = {}
+    for n in net.nodes:
+        if n.kind == "dethead":
+            stats[n.name] = _check_dethead(n, P, ref, grid[n.src])
+            continue
+        w, b = P[n.wname + ".weight"].astype(np.float64), P[n.wname + ".bias"].astype(np.float64)
+        g = grid[n.src] * lsb_of(w) * (0.25 if n.pre_avgpool else 1.0)
+        g = min(g, lsb_of(b))
+        if n.res is not None:
+            g = min(g, grid[n.res])
+        g_pre = g
+        if n.act == "prelu":
+            g *= lsb_of(P[n.wname + ".prelu"])
+        grid[n.name] = g
+        assert 2.0 ** -24 <= g <= 1.0, (n.name, g)
+        # finite values, everywhere
+        assert np.abs(raw[n.name]).max() < F16_MAX and np.isfinite(ref[n.name]).all(), (n.name, np.abs(raw[n.name]).max())
+        if n.name in onchip:                            # kept on chip by a fused op: the same number as fp16 and as fp32
+            assert _is_f16(raw[n.name]).all(), (n.name, "on-chip intermediate needs rounding", np.abs(raw[n.name]).max() / g)
+        if n.name not in probed and n.name not in onchip:
+            continue
+        # dyadic grid: every operand of the node is a multiple of its tracked lsb
+        assert _on_grid(ref[n.src], grid[n.src]) and _on_grid(w, lsb_of(w)) and _on_grid(b, g_pre), n.name
+        assert n.res is None or _on_grid(ref[n.res], grid[n.res]), n.name
+        assert _on_grid(raw[n.name], g), n.name
+        # partial sums: no subset of the addends, in any order, leaves the 24-bit window
+        x = _nchw(np.abs(ref[n.src]))
+        if n.pre_avgpool:
+            x = F.avg_pool2d(x, 2, 2)
+        S = F.conv2d(x, torch.from_numpy(np.abs(w)), torch.from_numpy(np.abs(b)), n.stride, n.pad, 1, n.groups)
+        if n.res is not None:
+            r = _nchw(np.abs(ref[n.res]))
+            S = S + (F.interpolate(r, scale_factor=2, mode="nearest") if n.res_up2 else r)
+        bits = float(np.log2(S.max().item() / g))
+        assert S.max().item() / g < GUARD, (n.name, bits)
+        st = dict(grid=g, sum_bits=bits, max=float(np.abs(raw[n.name]).max()))
+        if n.name in probed:
+            y, h = raw[n.name], ref[n.name]
+            inexact = h != y
+            with np.errstate(over="ignore"):
+                h16 = h.astype(np.float16)
+                up = np.nextafter(h16, np.float16(np.inf)).astype(np.float64)
+                dn = np.nextafter(h16, np.float16(-np.inf)).astype(np.float64)
+            tie = inexact & ((np.abs(y - h) * 2 == np.abs(up - h)) | (np.abs(y - h) * 2 == np.abs(h - dn)))
+            st.update(inexact=float(inexact.mean()), ties=float(tie.mean()), nonzero=float((h != 0).mean()))
+            assert st["inexact"] >= 0.10 and st["ties"] >= 0.01 and st["nonzero"] >= 0.20, (n.name, st)
+            if n.act == "prelu":
+                pre = eval_node(_no_act(n), ref, P)
+                st["negative"] = float((pre < 0).mean())
+                assert (pre < 0).any() and (pre > 0).any(), n.name
+            if n.groups == 1:                                 # every (tap, input channel) column reaches some cout of every 64-cout block
+                for c0 in range(0, n.cout, 64):
+                    assert (np.abs(w[c0:c0 + 64]).sum(axis=0) > 0).all(), (n.name, c0)
+            else:
+                assert (w != 0).all(), n.name
+        stats[n.name] = st
+    return stats
+
+
+def _check_dethead(n, P, ref, g_src):
+    """the bbox / kps channels of a DetHead: fp32 stores of exact sums (no rounding to see, so only grid, partial sums and coverage)"""
+    st = {}
+    for part in ("bbox", "kps"):
+        w, b = P[f"{n.wname}.{part}.weight"].astype(np.float64), P[f"{n.wname}.{part}.bias"].astype(np.float64)
+        g = min(g_src * lsb_of(w), lsb_of(b))
+        assert _on_grid(ref[n.src], g_src) and float(P[n.wname + ".bbox.scale"][0]) == 1.0
+        S = F.conv2d(_nchw(np.abs(ref[n.src])), torch.from_numpy(np.abs(w)), torch.from_numpy(np.abs(b)), 1, n.k // 2)
+        assert S.max().item() / g < GUARD, (n.name, part)
+        y = ref[n.name][1 if part == "bbox" else 2]
+        assert _on_grid(y, g) and (y != 0).mean() >= 0.20 and (np.abs(w).sum(axis=0) > 0).all(), (n.name, part)
+        st[part] = dict(grid=g, sum_bits=float(np.log2(S.max().item() / g)), max=float(np.abs(y).max()))
+    return st
+
+
+def _no_act(n):
+    import dataclasses
+    return dataclasses.replace(n, act="none")
+
+
+# ---- the comparator ----------------------------------------------------------------------------------------------------------------------
+
+def _ordered(h16):
+    b = h16.view(np.uint16).astype(np.int32)
+    return np.where(b & 0x8000, -(b & 0x7FFF), b & 0x7FFF)
+
+
+def assert_same_bits(got, ref, what=""):
+    """got, ref: [B, H, W, C] arrays holding fp16 values.  Both finite, then equal as fp16 (+0 == -0); no tolerance."""
+    got, ref = np.asarray(got), np.asarray(ref)
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    assert np.isfinite(got).all() and np.isfinite(ref).all(), f"{what}: not finite"
+    g, r = got.astype(np.float16), ref.astype(np.float16)
+    assert np.array_equal(g.astype(got.dtype), got) and np.array_equal(r.astype(ref.dtype), ref), f"{what}: not fp16 values"
+    if np.array_equal(g, r):
+        return
+    bad = np.argwhere(g != r)
+    ulps = _ordered(g) - _ordered(r)
+    vals, counts = np.unique(ulps[g != r], return_counts=True)
+    first = ", ".join(f"(n={i}, y={y}, x={x}, c={c}): got 0x{int(g[i, y, x, c].view(np.uint16)):04x} ref 0x{int(r[i, y, x, c].view(np.uint16)):04x}"
+                      for i, y, x, c in bad[:6])
+    hist = ", ".join(f"{int(v):+d}: {int(k)}" for v, k in zip(vals[:12], counts[:12]))
+    raise AssertionError(f"{what}: {len(bad)} of {g.size} values differ; first {first}; difference in fp16 ulps {{{hist}}}")
+
+
+def assert_same_values(got, ref, what=""):
+    """fp32 tensors (the detector head's bbox / kps channels): finite and equal, no tolerance"""
+    got, ref = np.asarray(got), np.asarray(ref)
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    assert np.isfinite(got).all() and np.isfinite(ref).all(), f"{what}: not finite"
+    bad = np.argwhere(got != ref)
+    if len(bad):
+        i = tuple(bad[0])
+        raise AssertionError(f"{what}: {len(bad)} of {got.size} values differ; first at {i}: got {got[i]!r} ref {ref[i]!r}")
+
+
+# ---- the probe nets ----------------------------------------------------------------------------------------------------------------------
+
+@dataclass
+class Probe:
+    name: str
+    net: Net
+    P: Dict[str, np.ndarray]
+    images: np.ndarray
+    probed: List[str]                        # nodes compared bit for bit whose conditions check_exactness asserts
+    onchip: List[str] = field(default_factory=list)     # nodes a fused op keeps on chip
+    env: Dict[str, str] = field(default_factory=dict)
+
+    @property
+    def batch(self):
+        return self.images.shape[0]
+
+
+KW = dict(bias=True, post_bn=False)
+
+
+def _net(hw):
+    return Net("t", tuple(hw), IN_MEAN, IN_SCALE)
+
+
+def _front(net, cin, layers):
+    """s (3 -> 64, 3x3, ReLU) [-> x (1x1, 64 -> cin, PReLU)]: the name of the tensor the op under test reads"""
+    net.add(Conv("s", "input", 3, 64, act="relu", **KW))
+    if cin == 64:
+        return "s"
+    net.add(Conv("x", "s", 64, cin, k=1, pad=0, act="prelu", **KW))
+    layers.setdefault("x", dict(density=0.25, mags=(1,)))
+    return "x"
+
+
+def family_probe(hw, cin, cout, batch, stride=1):
+    """both forms of a 3x3 conv on one input: c (cin -> cout, PReLU) and r (ReLU, + residual: the input itself at stride 1, a 1x1 / stride-2
+    conv d of it at stride 2)"""
+    net, layers = _net(hw), {}
+    x = _front(net, cin, layers)
+    net.add(Conv("c", x, cin, cout, stride=stride, act="prelu", **KW))
+    if stride == 1:
+        net.add(Conv("r", x, cin, cin, act="relu", res=x, **KW))
+        outs = [x, "c", "r"]
+    else:
+        net.add(Conv("d", x, cin, cout, k=1, stride=2, pad=0, **KW))
+        net.add(Conv("r", x, cin, cout, stride=2, act="relu", res="d", **KW))
+        outs = [x, "d", "c", "r"]
+    net.outputs = outs
+    dense = dict(density=1.0, mags=(1, 2, 3, 4, 5, 6, 7)) if cin == 64 else {}     # (576 taps on integers: larger factors, so that most sums need rounding)
+    layers.update(c=dict(bias=64, **dense), r=dict(bias=64, **dense))
+    name = f"conv{'.s2' if stride == 2 else ''}-{hw[0]}x{hw[1]}-{cin}-{cout}x{batch}"
+    return Probe(name, net, int_params(net, 7, layers), int_images(3, batch, hw), ["c", "r"])
+
+
+FAMILY_SHAPES = [((37, 21), 64, 64, 3), ((14, 14), 128, 128, 5), ((20, 20), 224, 224, 3), ((28, 28), 128, 256, 5), ((40, 24), 88, 224, 2)]
+MOSAIC_SHAPES = [((7, 7), 128, 128, 9)]
+STRIDE2_SHAPES = [((37, 45), 64, 96, 2), ((30, 18), 96, 64, 3)]
+
+
+@functools.lru_cache(maxsize=None)
+def get_family_probe(hw, cin, cout, batch, stride=1):
+    return family_probe(hw, cin, cout, batch, stride)
+
+
+@functools.lru_cache(maxsize=None)
+def cached_reference(probe_key):
+    """(ref, raw) of a probe built by PROBES[probe_key]: computed once, shared by every test that needs it, never written to"""
+    p = PROBES[probe_key]()
+    raw = {}
+    ref = reference(p.net, p.P, p.images, raw)
+    for a in list(ref.values()) + list(raw.values()):
+        for b in (a if isinstance(a, tuple) else (a,)):
+            b.setflags(write=False)
+    return ref, raw
+
+
+PROBES = {}
+
+
+def _register(fn, *args):
+    p = fn(*args)
+    PROBES[p.name] = functools.partial(fn, *args)
+    return p.name
+
+
+FAMILY_KEYS = {sh: _register(get_family_probe, *sh) for sh in FAMILY_SHAPES + MOSAIC_SHAPES}
+STRIDE2_KEYS = {sh: _register(get_family_probe, *sh, 2) for sh in STRIDE2_SHAPES}
+
+
+# ---- fused ops ---------------------------------------------------------------------------------------------------------------------------
+# An intermediate map that a fused op keeps on chip (Probe.onchip) must be the same number as fp16 and as fp32: the layers in front of it are
+# sparse (few +-1 taps) and the images of these nets come from a narrower band, so that it stays inside fp16's 11 bits.  The last conv of the
+# op is dense with factors up to 7: most of ITS sums need rounding.
+
+DENSE = dict(density=1.0, mags=(1, 2, 3, 4, 5, 6, 7), bias=64)
+FINE = dict(density=1.0, mags=tuple(range(1, 32)), exp=-2, bias=64)     # quarters up to 7.75: for a 1x1 conv on small integers
+NARROW = (126, 130)                   # |2 p - 255| <= 3
+
+
+def _narrow_images(seed, batch, hw):
+    return np.random.default_rng(seed).integers(NARROW[0], NARROW[1], (batch,) + tuple(hw) + (3,), dtype=np.uint8)
+
+
+def bb_probe(hw, planes, batch):
+    """a residual BasicBlock (conv3x3 + ReLU, conv3x3, + block input, ReLU): csrc/conv_bb.hip keeps b.conv1 on chip"""
+    net = _net(hw)
+    net.add(Conv("s", "input", 3, planes, act="relu", **KW))
+    net.add(Conv("b.conv1", "s", planes, planes, act="relu", **KW))
+    net.add(Conv("b.conv2", "b.conv1", planes, planes, act="relu", res="s", **KW))
+    net.outputs = ["s", "b.conv2"]
+    layers = {"s": dict(density=1.0 / 3.0), "b.conv1": dict(density=8.0 / planes, mags=(1,)), "b.conv2": dict(density=1.0, mags=(1, 2, 3), bias=64)}
+    return Probe(f"bb-{hw[0]}x{hw[1]}-{planes}x{batch}", net, int_params(net, 11, layers), int_images(5, batch, hw), ["b.conv2"], ["b.conv1"])
+
+
+def mbf_probe(hw, cin, g, cout, stride, res, act3, batch):
+    """MobileFaceNet's bottleneck (1x1 -> depthwise 3x3 -> 1x1 [+ block input]): csrc/mbf_block.hip keeps b.pw1 and b.dw on chip"""
+    net = _net(hw)
+    net.add(Conv("s", "input", 3, 64, act="relu", **KW))
+    x = "s"
+    if cin != 64:
+        x = net.add(Conv("x", "s", 64, cin, k=1, pad=0, act="relu", **KW))
+    net.add(Conv("b.pw1", x, cin, g, k=1, pad=0, act="relu", **KW))
+    net.add(Conv("b.dw", "b.pw1", g, g, stride=stride, groups=g, act="relu", **KW))
+    net.add(Conv("b.pw2", "b.dw", g, cout, k=1, pad=0, act=act3, res=x if res else None, **KW))
+    net.outputs = [x, "b.pw2"]
+    sparse = lambda c: dict(density=8.0 / c, mags=(1,))
+    layers = {"s": dict(density=1.0 / 3.0), "x": sparse(64), "b.pw1": sparse(cin), "b.dw": dict(mags=(1,)), "b.pw2": FINE}
+    return Probe(f"mbf-{hw[0]}x{hw[1]}-{cin}-{g}-{cout}s{stride}x{batch}", net, int_params(net, 13, layers), _narrow_images(6, batch, hw),
+                 ["b.pw2"], ["b.pw1", "b.dw"], {})
+
+
+def dwpw_probe(hw, g, cout, stride, act1, batch):
+    """depthwise 3x3 + the pointwise 1x1 behind it: csrc/dwpw.hip (FID_DWPW_FUSE=1) keeps dw on chip"""
+    net = _net(hw)
+    net.add(Conv("s", "input", 3, 64, act="relu", **KW))
+    net.add(Conv("p1", "s", 64, g, k=1, pad=0, act="relu", **KW))
+    net.add(Conv("dw", "p1", g, g, stride=stride, groups=g, act=act1, **KW))
+    net.add(Conv("pw", "dw", g, cout, k=1, pad=0, act="prelu", **KW))
+    net.outputs = ["p1", "pw"]
+    layers = {"s": dict(density=1.0 / 3.0), "p1": dict(density=1.0 / 8.0, mags=(1,)), "dw": dict(mags=(1, 2)), "pw": FINE}
+    return Probe(f"dwpw-{hw[0]}x{hw[1]}-{g}-{cout}s{stride}x{batch}", net, int_params(net, 15, layers), _narrow_images(7, batch, hw),
+                 ["pw"], ["dw"], {"FID_NO_MBF_FUSE": "1"})
+
+
+def dual_probe(hw, planes, batch):
+    """the block shortcut (2x2 average pool + 1x1 conv: the weights become quarters) beside the stride-2 conv on the same input: conv_s2.hip DUAL"""
+    net = _net(hw)
+    net.add(Conv("s", "input", 3, 64, act="relu", **KW))
+    net.add(Conv("b.down", "s", 64, planes, k=1, stride=1, pad=0, pre_avgpool=True, **KW))
+    net.add(Conv("b.conv1", "s", 64, planes, stride=2, act="relu", **KW))
+    net.outputs = ["s", "b.down", "b.conv1"]
+    return Probe(f"dual-{hw[0]}x{hw[1]}-{planes}x{batch}", net, int_params(net, 17, {"b.down": DENSE, "b.conv1": DENSE}), int_images(8, batch, hw),
+                 ["b.down", "b.conv1"])
+
+
+def stem_probe(hw, act, batch):
+    """IResNet's stem + the 3x3 conv on it + the block's 1x1 / stride-2 shortcut: csrc/stem_block.hip keeps the stem's map on chip and stores
+    its even pixels"""
+    net = _net(hw)
+    net.add(Conv("stem", "input", 3, 64, act=act, **KW))
+    net.add(Conv("b.down", "stem", 64, 64, k=1, stride=2, pad=0, **KW))
+    net.add(Conv("b.conv1", "stem", 64, 64, act=act, **KW))
+    net.outputs = ["b.down", "b.conv1"]
+    return Probe(f"stem-{hw[0]}x{hw[1]}-{act}x{batch}", net, int_params(net, 19, {"b.down": FINE, "b.conv1": DENSE}), int_images(9, batch, hw),
+                 ["b.down", "b.conv1"], ["stem"])
+
+
+def dw_probe(hw, batch):
+    """a depthwise 3x3 layer of its own (net.hip: dwconv_nhwc; dwconv3x3_lds from 50 000 pixels per launch)"""
+    net = _net(hw)
+    net.add(Conv("s", "input", 3, 64, act="relu", **KW))
+    net.add(Conv("p", "s", 64, 64, k=1, pad=0, act="prelu", **KW))
+    net.add(Conv("d", "p", 64, 64, groups=64, act="prelu", **KW))
+    net.outputs = ["p", "d"]
+    return Probe(f"dw-{hw[0]}x{hw[1]}x{batch}", net, int_params(net, 21, {"p": dict(density=0.25, mags=(1,)), "d": DENSE}), int_images(10, batch, hw), ["d"])
+
+
+def latfpn_probe(hw, batch):
+    """two PAFPN levels and the coarsest one (lateral 1x1 [+ the upsampled coarser lateral] -> 3x3): csrc/lat_fpn.hip keeps the laterals on chip
+    and stores the ones a finer level adds.  The laterals are compared as well, but only the 3x3 convs are held to the power conditions."""
+    net = _net(hw)
+    net.add(Conv("s", "input", 3, 32, act="relu", **KW))
+    net.add(Conv("c3", "s", 32, 88, act="relu", **KW))
+    net.add(Conv("c4", "c3", 88, 88, stride=2, act="relu", **KW))
+    net.add(Conv("c5", "c4", 88, 88, stride=2, act="relu", **KW))
+    net.add(Conv("lat2", "c5", 88, 56, k=1, pad=0, **KW))
+    net.add(Conv("lat1", "c4", 88, 56, k=1, pad=0, res="lat2", res_up2=True, **KW))
+    net.add(Conv("lat0", "c3", 88, 56, k=1, pad=0, res="lat1", res_up2=True, **KW))
+    for i in range(3):
+        net.add(Conv(f"fpn{i}", f"lat{i}", 56, 56, **KW))
+    net.outputs = ["c3", "c4", "c5", "fpn0", "fpn1", "fpn2"]
+    few = lambda taps: dict(density=4.0 / taps, mags=(1,))
+    layers = {"s": dict(density=1.0 / 3.0), "c3": few(288), "c4": few(792), "c5": few(792), "lat0": few(88), "lat1": few(88), "lat2": few(88)}
+    layers.update({f"fpn{i}": dict(density=1.0, mags=(1, 2, 3), bias=64) for i in range(3)})
+    return Probe(f"latfpn-{hw[0]}x{hw[1]}x{batch}", net, int_params(net, 23, layers), _narrow_images(11, batch, hw),
+                 ["fpn0", "fpn1", "fpn2"], ["lat0", "lat1", "lat2"])
+
+
+def shortcut_probe(hw, cin, cout, batch):
+    """a downsampling block whose 1x1 / stride-2 shortcut conv2 may absorb as extra K-steps (a generation-12 pick; conv_s2.hip NX = 2 with ns = 10):
+    the absorbed form never rounds b.down, so b.down counts as kept on chip"""
+    net, layers = _net(hw), {}
+    x = _front(net, cin, layers)
+    net.add(Conv("b.down", x, cin, cout, k=1, stride=2, pad=0, **KW))
+    net.add(Conv("b.conv1", x, cin, cout, act="prelu", **KW))
+    net.add(Conv("b.conv2", "b.conv1", cout, cout, stride=2, res="b.down", **KW))
+    net.outputs = [x, "b.conv1", "b.conv2"]
+    layers.update({"b.down": dict(density=8.0 / cin, mags=(1,)), "b.conv1": dict(density=8.0 / (9 * cin), mags=(1,))})
+    return Probe(f"shortcut-{hw[0]}x{hw[1]}-{cin}-{cout}x{batch}", net, int_params(net, 25, layers), int_images(12, batch, hw), ["b.conv2"], ["b.down"])
+
+
+def dethead_probe(hw, cin, batch):
+    """the detector head conv (2 + 8 + 20 fp32 channels): the bbox and kps channels are exact sums; the sigmoid scores stay with the tolerance test"""
+    from scrfd_arcface_facerecognition_amd.archs import DetHead
+    net, layers = _net(hw), {}
+    x = _front(net, cin, layers)
+    net.add(DetHead("h", x, cin, 8))
+    net.outputs = [x, "h"]
+    return Probe(f"dethead-{hw[0]}x{hw[1]}-{cin}x{batch}", net, int_params(net, 27, layers), int_images(13, batch, hw), [])
+
+
+BB_SHAPES = [((37, 45), 64, 2), ((12, 20), 64, 5), ((37, 45), 32, 2), ((12, 20), 24, 5)]
+MBF_SHAPES = [((30, 22), 64, 96, 64, 1, True, "relu", 1), ((37, 21), 64, 128, 96, 2, False, "prelu", 2), ((14, 14), 256, 512, 256, 2, False, "none", 3)]
+DWPW_SHAPES = [((37, 21), 64, 96, 1, "relu", 1), ((16, 24), 32, 48, 2, "none", 4)]
+DUAL_SHAPES = [((74, 50), 96, 2)]
+STEM_SHAPES = [((50, 44), "relu", 2), ((16, 16), "prelu", 1)]
+DW_SHAPES = [((113, 75), 6), ((37, 21), 2)]            # 6 x 113 x 75 = 50 850 pixels: the LDS-tiled kernel, ragged tiles both ways
+
+LATFPN_SHAPES = [((40, 56), 3), ((16, 16), 1)]
+SHORTCUT_SHAPES = [((37, 45), 64, 96, 2), ((28, 28), 64, 128, 3)]
+
+DETHEAD_SHAPES = [((24, 40), 80, 2), ((26, 26), 64, 3)]
+BB_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(bb_probe), *sh) for sh in BB_SHAPES}
+MBF_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(mbf_probe), *sh) for sh in MBF_SHAPES}
+DWPW_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(dwpw_probe), *sh) for sh in DWPW_SHAPES}
+DUAL_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(dual_probe), *sh) for sh in DUAL_SHAPES}
+STEM_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(stem_probe), *sh) for sh in STEM_SHAPES}
+DW_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(dw_probe), *sh) for sh in DW_SHAPES}
+LATFPN_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(latfpn_probe), *sh) for sh in LATFPN_SHAPES}
+SHORTCUT_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(shortcut_probe), *sh) for sh in SHORTCUT_SHAPES}
+DETHEAD_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(dethead_probe), *sh) for sh in DETHEAD_SHAPES}
