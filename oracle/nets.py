@@ -19,28 +19,30 @@ def _bn(x, P, prefix):
 
 
 @torch.no_grad()
-def run_net(net, P, blob, keep=None, dtype=torch.float32, store=None):
+def run_net(net, P, blob, keep=None, dtype=torch.float32, store=None, bn=None):
     """blob: float32 [N,3,H,W] (already normalised, RGB).  Returns {name: np.ndarray} for the net
     outputs (plus any tensor named in `keep`).  DetHead outputs are (scores[N,HWA,1],
     bbox[N,HWA,4], kps[N,HWA,10]) like the 9 ONNX outputs of SCRFD.
     dtype: the precision the net is evaluated in.  store: None, or store(name, y) -> y applied to the result of
     every conv / maxpool node, the tensors the executor keeps as fp16 (tests/exact_probe.py rounds them there, in
-    float64: the exact reference).  FC and DetHead results are fp32 tensors on the device and do not pass through it."""
+    float64: the exact reference).  FC and DetHead results are fp32 tensors on the device and do not pass through it.
+    bn: None (BatchNorm as BatchNorm), or bn(x, prefix) -> y in its place (tests/exact_probe.py: the ideal affine of its probe parameters)."""
     t = {"input": torch.from_numpy(np.ascontiguousarray(blob)).to(dtype)}
     par = lambda k: torch.from_numpy(P[k]).to(dtype)
     stored = (lambda name, y: y) if store is None else store
+    norm = (lambda x, prefix: _bn(x, P, prefix)) if bn is None else bn
     for n in net.nodes:
         x = t[n.src]
         if n.kind == "conv":
             w = n.wname
             if n.pre_bn:
-                x = _bn(x, P, w + ".pre_bn")
+                x = norm(x, w + ".pre_bn")
             if n.pre_avgpool:
                 x = F.avg_pool2d(x, 2, 2)
             b = par(w + ".bias") if n.bias else None
             y = F.conv2d(x, par(w + ".weight"), b, n.stride, n.pad, 1, n.groups)
             if n.post_bn:
-                y = _bn(y, P, w + ".post_bn")
+                y = norm(y, w + ".post_bn")
             if n.res is not None:
                 r = t[n.res]
                 if n.res_up2:
@@ -56,12 +58,12 @@ def run_net(net, P, blob, keep=None, dtype=torch.float32, store=None):
         elif n.kind == "fc":
             w = n.wname
             if n.pre_bn:
-                x = _bn(x, P, w + ".pre_bn")
+                x = norm(x, w + ".pre_bn")
             y = x.flatten(1) @ par(w + ".weight").T
             if n.bias:
                 y = y + par(w + ".bias")
             if n.post_bn:
-                y = _bn(y, P, w + ".post_bn")
+                y = norm(y, w + ".post_bn")
             t[n.name] = y
         elif n.kind == "dethead":
             w, A = n.wname, n.num_anchors

@@ -5,14 +5,22 @@ every partial sum of its convolution is exactly representable in fp32: the fp32 
 order, the tile shape, the K split or the MFMA shape, and the stored fp16 value is the round-to-nearest-even of ONE exact number.  A float64
 reference that rounds every node to fp16 states it bit for bit -- for every kernel variant, whichever variant runs the layers in front.
 
-  int_params       such parameters for a Net whose nodes carry no BatchNorm (bias=True, post_bn=False, pre_bn=False)
-  reference        the net in float64, every fp16 tensor rounded with numpy's astype(np.float16) (oracle.nets.run_net(dtype, store))
+  int_params       such weights, biases (where a node has one) and slopes for a Net
+  bn_params        BatchNorm parameters whose fold is such a layer again: scale = +-2 ** k, zero running mean, integer shift (below)
+  reference        the net in float64, every fp16 tensor rounded with numpy's astype(np.float16) and every BatchNorm evaluated as its ideal
+                   affine (oracle.nets.run_net(dtype, store, bn))
   check_exactness  the CONDITIONS under which the comparison may be exact and can see a fault, asserted on the reference alone
   assert_same_bits the comparator: finite, then equality of the fp16 values (+0 == -0), with positions / bit patterns / ulp histogram on failure
   PROBES           the probe nets: a 3 -> 64 stem, a 1x1 widening conv where the op needs more channels, then the op under test
 
-BatchNorm is out of scope: gamma / sqrt(var + eps) cannot be made an exact power of two, so the folded forms (IResNet's "ir" block with its
-border-class bias rows, a shortcut conv with BN) stay with the tolerance tests."""
+BatchNorm with a zero running mean is in scope.  gamma / sqrt(var + eps) is no exact power of two, but exactness only needs the constants the
+device RECEIVES to be the ideal ones: with var = float32(1 - 1e-5) and gamma = +-2 ** k the scale is 2 ** k (1 + d), |d| < 2 ** -26, and the fp16
+folded weights W a1 a2 and the fp32 bias rows round to the values of the ideal affine x * gamma + beta (test_exact_probe_cpu.py lowers every BN
+probe both ways and compares the blobs byte for byte).  Two constraints keep a bias row from cancelling down to a ~1e-7 residue where the
+ideal value is 0: running means are 0, and a conv with a BatchNorm in front has a post-BN whose shift is 0.  The BN nodes carry no conv bias
+(as in IResNet).  A BatchNorm in front of a zero-padded 3x3 conv folds into NINE bias rows, one per border class (lower.py fold_conv): fold_node
+states that fold, eval_node applies it per pixel, and check_exactness asserts that a wrong class at any border pixel changes a stored value.
+Nonzero running means stay with the tolerance tests."""
 import functools
 from dataclasses import dataclass, field
 from typing import Dict, List
@@ -46,18 +54,97 @@ def int_params(net, seed, layers=None):
                 P[f"{n.wname}.{part}.bias"] = rng.integers(-64, 65, c).astype(np.float32)
             P[n.wname + ".bbox.scale"] = np.ones(1, np.float32)
             continue
-        assert n.kind == "conv" and n.bias and not n.post_bn and not n.pre_bn, n.name
-        o = dict(density=1.0 if (n.src == "input" or n.groups > 1) else 1.0 / 3.0, mags=(1,) if n.src == "input" else (1, 2), exp=0, bias=8)
+        assert n.kind == "conv", n.name                       # (a node's BatchNorms: bn_params)
+        o = dict(density=1.0 if (n.src == "input" or n.groups > 1) else 1.0 / 3.0, mags=(1,) if n.src == "input" else (1, 2), exp=0, bias=8,
+                 slopes=(0.5, 0.25))
         o.update((layers or {}).get(n.name, {}))
         shape = (n.cout, n.cin // n.groups, n.k, n.k)
         w = rng.choice(o["mags"], shape) * rng.choice([-1, 1], shape) * (rng.random(shape) < o["density"])
         P[n.wname + ".weight"] = (w * 2.0 ** o["exp"]).astype(np.float32)
-        P[n.wname + ".bias"] = (rng.integers(-o["bias"], o["bias"] + 1, n.cout) * 2.0 ** o["exp"]).astype(np.float32)
+        if n.bias:
+            P[n.wname + ".bias"] = (rng.integers(-o["bias"], o["bias"] + 1, n.cout) * 2.0 ** o["exp"]).astype(np.float32)
         if n.act == "prelu":
-            P[n.wname + ".prelu"] = rng.choice([0.5, 0.25], n.cout).astype(np.float32)
+            P[n.wname + ".prelu"] = rng.choice(o["slopes"], n.cout).astype(np.float32)
     for k, v in P.items():
         assert np.array_equal(v.astype(np.float16).astype(np.float32), v), k
     return P
+
+
+BN_VAR = np.float32(1.0 - 1e-5)         # + BN_EPS = 1 + d, |d| < 2 ** -25: the scale gamma / sqrt(var + eps) is gamma (1 + d / 2)
+
+
+def bn_params(net, seed, layers=None):
+    """{name: float32 array} for every BatchNorm of `net` (prefix <wname>.pre_bn / <wname>.post_bn): gamma = a signed power of two from `scales`
+    per channel, var = BN_VAR, mean = 0, beta = integers in +-`beta` -- on the BN in front as well, so that the nine bias rows differ -- and 0
+    on the post-BN of a conv that has a BN in front.  layers: {"<node name>.pre_bn" | "<node name>.post_bn": overrides of scales / beta}."""
+    rng = np.random.default_rng(seed)
+    P = {}
+    for n in net.nodes:
+        if n.kind != "conv":
+            continue
+        for which, c in (("pre_bn", n.cin), ("post_bn", n.cout)):
+            if not getattr(n, which):
+                continue
+            assert not n.bias, n.name                         # (bias a2 (1 + d) + beta2 would cancel: see the module docstring)
+            o = dict(scales=(1.0, 0.5), beta=8)
+            o.update((layers or {}).get(f"{n.name}.{which}", {}))
+            pre = f"{n.wname}.{which}"
+            P[pre + ".gamma"] = (rng.choice(o["scales"], c) * rng.choice([-1, 1], c)).astype(np.float32)
+            P[pre + ".var"] = np.full(c, BN_VAR, np.float32)
+            P[pre + ".mean"] = np.zeros(c, np.float32)
+            beta = rng.integers(-o["beta"], o["beta"] + 1, c)
+            P[pre + ".beta"] = (beta * (0 if which == "post_bn" and n.pre_bn else 1)).astype(np.float32)
+    return P
+
+
+def ideal_affine(P, prefix):
+    """(A, B) of a bn_params BatchNorm as the affine x * A + B it stands for, float64"""
+    assert (P[prefix + ".mean"] == 0).all() and (P[prefix + ".var"] == BN_VAR).all(), prefix
+    a = P[prefix + ".gamma"].astype(np.float64)
+    m, e = np.frexp(np.abs(a))
+    assert (m == 0.5).all(), prefix                           # signed powers of two
+    return a, P[prefix + ".beta"].astype(np.float64)
+
+
+INTERIOR, TOP_LEFT, TOP = 4, 0, 1       # border classes (row class * 3 + column class; 0: first row / column, 2: last, 1: between)
+
+
+def border_classes(H, W):
+    """int [H, W]: the border class of every pixel of a zero-padded 3x3 / stride-1 conv's map"""
+    assert H >= 2 and W >= 2
+    yc = np.where(np.arange(H) == 0, 0, np.where(np.arange(H) == H - 1, 2, 1))
+    xc = np.where(np.arange(W) == 0, 0, np.where(np.arange(W) == W - 1, 2, 1))
+    return yc[:, None] * 3 + xc[None, :]
+
+
+def fold_node(n, P):
+    """(W [cout, cin / groups, k, k], bias rows [1 or 9, cout]) of a conv node, float64: the layer the device is given.  A BatchNorm in front
+    scales the input channels and shifts every tap that lies INSIDE the map: one bias row per border class where the conv pads; the BatchNorm
+    behind scales the output channels and shifts the rows.  (An average pool in front stays with the caller.)"""
+    W = P[n.wname + ".weight"].astype(np.float64)
+    rows = (P[n.wname + ".bias"].astype(np.float64) if n.bias else np.zeros(n.cout))[None, :]
+    if n.pre_bn:
+        assert n.groups == 1 and not n.pre_avgpool, n.name
+        a1, b1 = ideal_affine(P, n.wname + ".pre_bn")
+        shift = np.einsum("oikl,i->okl", W, b1)                # what the shift adds through every tap
+        W = W * a1[None, :, None, None]
+        if n.pad == 0:
+            rows = rows + shift.sum(axis=(1, 2))[None, :]
+        else:
+            assert n.k == 3 and n.pad == 1 and n.stride == 1, n.name
+            inside = np.ones((9, 3, 3))
+            for cls in range(9):
+                yc, xc = divmod(cls, 3)
+                if yc != 1:
+                    inside[cls, yc, :] = 0                    # the first row has no row above it, the last one none below
+                if xc != 1:
+                    inside[cls, :, xc] = 0
+            rows = rows + np.einsum("okl,ckl->co", shift, inside)
+    if n.post_bn:
+        a2, b2 = ideal_affine(P, n.wname + ".post_bn")
+        W = W * a2[:, None, None, None]
+        rows = rows * a2[None, :] + b2[None, :]
+    return W, rows
 
 
 def int_images(seed, batch, hw):
@@ -83,8 +170,12 @@ def reference(net, P, images, raw=None):
         out[name] = r.permute(0, 2, 3, 1).numpy().copy()
         return r
 
+    def bn(x, prefix):                                       # the ideal affine, not x / sqrt(var + eps): that lies 1e-9 off the grid and breaks ties
+        a, b = ideal_affine(P, prefix)
+        return x * torch.from_numpy(a)[None, :, None, None] + torch.from_numpy(b)[None, :, None, None]
+
     blob = align.blob_from_images(list(images), net.in_scale, net.in_mean)
-    res = onets.run_net(net, P, blob, keep=[n.name for n in net.nodes], dtype=torch.float64, store=store)
+    res = onets.run_net(net, P, blob, keep=[n.name for n in net.nodes], dtype=torch.float64, store=store, bn=bn)
     for n in net.nodes:
         if n.kind == "dethead":                               # an fp32 tensor on the device: (scores, bbox, kps) as float64, not rounded
             out[n.name] = res[n.name]
@@ -114,21 +205,25 @@ def _chunks(n):
 
 
 def eval_node(n, ref, P, mode="exact", rounded=True):
-    """One conv node from the reference's STORED inputs, [B, H, W, C] as float64 holding fp16 values.  mode:
+    """One conv node from the reference's STORED inputs, [B, H, W, C] as float64 holding fp16 values, in its FOLDED form (fold_node: the weights
+    and the bias row of every pixel's border class, as the device computes it; the reference applies the BatchNorms as they stand).  mode:
       exact          float64, one conv
       f32_fwd        float32, the K axis in 32-channel chunks, first to last
       f32_rev        float32, the chunks last to first, the channels of every chunk flipped
       fault_tap      the centre tap does not reach pixel (0, 0) of image 0
       fault_f16acc   the partial sum is rounded to fp16 between the chunks
       fault_rtz      the store rounds toward zero
+      fault_border   every pixel takes the interior bias row (a node with border classes)
+      fault_class    the top-left corner pixel of the LAST image takes the top-edge row
     rounded=False: the float64 value before the store (the f32 modes always return the fp32 accumulator's value)"""
     dt = torch.float32 if mode.startswith("f32") else torch.float64
     x = _nchw(ref[n.src]).to(dt)
     if n.pre_avgpool:
         x = F.avg_pool2d(x, 2, 2)
-    w = torch.from_numpy(P[n.wname + ".weight"]).to(dt)
+    wf, rows = fold_node(n, P)
+    w = torch.from_numpy(wf).to(dt)
     conv = lambda xx, ww: F.conv2d(xx, ww, None, n.stride, n.pad, 1, n.groups)
-    if mode == "exact" or mode == "fault_rtz":
+    if mode in ("exact", "fault_rtz", "fault_border", "fault_class"):
         y = conv(x, w)
     elif mode == "fault_tap":
         y = conv(x, w)
@@ -151,7 +246,17 @@ def eval_node(n, ref, P, mode="exact", rounded=True):
             y = y + part
             if mode == "fault_f16acc":
                 y = _r16(y)
-    y = y + torch.from_numpy(P[n.wname + ".bias"]).to(dt)[None, :, None, None]
+    if rows.shape[0] == 1:
+        assert not mode.startswith("fault_border") and mode != "fault_class", n.name
+        y = y + torch.from_numpy(rows[0]).to(dt)[None, :, None, None]
+    else:
+        cls = np.broadcast_to(border_classes(y.shape[2], y.shape[3]), (y.shape[0], y.shape[2], y.shape[3])).copy()
+        if mode == "fault_border":
+            cls[:] = INTERIOR
+        elif mode == "fault_class":
+            assert cls[-1, 0, 0] == TOP_LEFT
+            cls[-1, 0, 0] = TOP
+        y = y + torch.from_numpy(rows[cls]).to(dt).permute(0, 3, 1, 2)
     if n.res is not None:
         r = _nchw(ref[n.res]).to(dt)
         if n.res_up2:
@@ -210,9 +315,22 @@ def check_exactness(net, P, images, probed, onchip=(), ref=None, raw=None):
         if n.kind == "dethead":
             stats[n.name] = _check_dethead(n, P, ref, grid[n.src])
             continue
-        w, b = P[n.wname + ".weight"].astype(np.float64), P[n.wname + ".bias"].astype(np.float64)
+        w, b = fold_node(n, P)                                # through both BatchNorms: the folded weights W a1 a2 and the bias rows
+        if n.pre_bn or n.post_bn:
+            assert _is_f16(w).all() and (np.abs(b) < 2.0 ** 24).all(), (n.name, "folded weights are not fp16 values")
         g = grid[n.src] * lsb_of(w) * (0.25 if n.pre_avgpool else 1.0)
         g = min(g, lsb_of(b))
+        if n.pre_bn or n.post_bn:                             # the same grid through both affines as they stand: x A1 + B1, conv, y A2 + B2
+            ga = grid[n.src]
+            if n.pre_bn:
+                a1, b1 = ideal_affine(P, n.wname + ".pre_bn")
+                ga = min(ga * lsb_of(a1), lsb_of(b1))
+            ga *= lsb_of(P[n.wname + ".weight"]) * (0.25 if n.pre_avgpool else 1.0)
+            if n.post_bn:
+                a2, b2 = ideal_affine(P, n.wname + ".post_bn")
+                ga = min(ga * lsb_of(a2), lsb_of(b2))
+            assert ga <= g and _on_grid(g, ga), (n.name, g, ga)     # (the fold can only be coarser: it multiplies the scales channel by channel)
+            g = ga
         if n.res is not None:
             g = min(g, grid[n.res])
         g_pre = g
@@ -224,6 +342,7 @@ def check_exactness(net, P, images, probed, onchip=(), ref=None, raw=None):
         assert np.abs(raw[n.name]).max() < F16_MAX and np.isfinite(ref[n.name]).all(), (n.name, np.abs(raw[n.name]).max())
         if n.name in onchip:                            # kept on chip by a fused op: the same number as fp16 and as fp32
             assert _is_f16(raw[n.name]).all(), (n.name, "on-chip intermediate needs rounding", np.abs(raw[n.name]).max() / g)
+        border = _check_border(n, ref, P, b) if b.shape[0] == 9 else None      # (every border-class node, probed or not)
         if n.name not in probed and n.name not in onchip:
             continue
         # dyadic grid: every operand of the node is a multiple of its tracked lsb
@@ -234,13 +353,15 @@ def check_exactness(net, P, images, probed, onchip=(), ref=None, raw=None):
         x = _nchw(np.abs(ref[n.src]))
         if n.pre_avgpool:
             x = F.avg_pool2d(x, 2, 2)
-        S = F.conv2d(x, torch.from_numpy(np.abs(w)), torch.from_numpy(np.abs(b)), n.stride, n.pad, 1, n.groups)
+        S = F.conv2d(x, torch.from_numpy(np.abs(w)), torch.from_numpy(np.abs(b).max(axis=0)), n.stride, n.pad, 1, n.groups)     # (the largest |bias row|)
         if n.res is not None:
             r = _nchw(np.abs(ref[n.res]))
             S = S + (F.interpolate(r, scale_factor=2, mode="nearest") if n.res_up2 else r)
         bits = float(np.log2(S.max().item() / g))
         assert S.max().item() / g < GUARD, (n.name, bits)
         st = dict(grid=g, sum_bits=bits, max=float(np.abs(raw[n.name]).max()))
+        if border is not None:
+            st["border"] = border
         if n.name in probed:
             y, h = raw[n.name], ref[n.name]
             inexact = h != y
@@ -262,6 +383,21 @@ def check_exactness(net, P, images, probed, onchip=(), ref=None, raw=None):
                 assert (w != 0).all(), n.name
         stats[n.name] = st
     return stats
+
+
+def _check_border(n, ref, P, rows):
+    """a node with nine border-class bias rows: the rows tell the classes apart, and a wrong class shows.  Every pair of rows differs in at
+    least a quarter of the output channels; at every border pixel of every image the interior row in place of the pixel's own changes the stored
+    fp16 value of some channel."""
+    share = min(float((rows[i] != rows[j]).mean()) for i in range(9) for j in range(i))
+    assert share >= 0.25, (n.name, "bias rows too much alike", share)
+    good, bad = eval_node(n, ref, P), eval_node(n, ref, P, "fault_border")
+    changed = (good != bad).any(axis=3)                       # [B, H, W]
+    is_border = border_classes(*changed.shape[1:]) != INTERIOR
+    assert not changed[:, ~is_border].any() and changed[:, is_border].all(), (n.name, "a border pixel the interior row does not change",
+                                                                             np.argwhere(~changed & is_border[None])[:4].tolist())
+    return dict(row_pairs_differ=share, border_pixels=int(is_border.sum()), pixels=int(is_border.size),
+                channels_changed=float((good != bad)[:, is_border].mean()))
 
 
 def _check_dethead(n, P, ref, g_src):
@@ -561,3 +697,77 @@ DW_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(dw_probe), *sh) for s
 LATFPN_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(latfpn_probe), *sh) for sh in LATFPN_SHAPES}
 SHORTCUT_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(shortcut_probe), *sh) for sh in SHORTCUT_SHAPES}
 DETHEAD_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(dethead_probe), *sh) for sh in DETHEAD_SHAPES}
+
+
+# ---- BatchNorm-folded forms --------------------------------------------------------------------------------------------------------------
+# IResNet's layers: no conv bias, BatchNorm behind every conv and in front of a block's first one.  The conv behind a BN in front is zero-padded,
+# so its bias is one of nine rows by the pixel's border class (lower.py: CF_BORDER); every kernel family decodes that class from its own tile
+# coordinates.  Parameters: bn_params (see the module docstring for what makes the lowered constants the ideal ones).
+
+BN = dict(bias=False, post_bn=True)
+TINY_SHAPES = [((3, 5), 64, 64, 7)]      # 13 of 15 pixels are border pixels and every class occurs; seven images side by side on a STRIP tile
+
+
+def _bn_probe(name, net, seed, layers, bn_layers, images, probed, onchip=()):
+    P = int_params(net, seed, layers)
+    P.update(bn_params(net, seed + 1, bn_layers))
+    return Probe(name, net, P, images, list(probed), list(onchip))
+
+
+def family_bn_probe(hw, cin, cout, batch):
+    """both BatchNorm forms of a 3x3 conv on one input: c (BN - conv - BN - PReLU, cin -> cout) and r (BN - conv - BN, + the input, no activation)"""
+    net, layers = _net(hw), {}
+    x = _front(net, cin, layers)
+    net.add(Conv("c", x, cin, cout, act="prelu", pre_bn=True, **BN))
+    net.add(Conv("r", x, cin, cin, res=x, pre_bn=True, **BN))
+    net.outputs = [x, "c", "r"]
+    dense = dict(density=1.0, mags=(1, 2, 3, 4, 5, 6, 7)) if cin == 64 else {}
+    layers.update(c=dict(dense), r=dict(dense))
+    one = {"c.post_bn": dict(scales=(1.0,))} if cin > 128 else {}     # (2016 taps: one magnitude behind c keeps its partial sums inside GUARD)
+    return _bn_probe(f"convbn-{hw[0]}x{hw[1]}-{cin}-{cout}x{batch}", net, 29, layers, one, int_images(14, batch, hw), ["c", "r"])
+
+
+def ir_probe(hw, planes, batch):
+    """IResNet's residual block (BN - conv - BN - PReLU - conv - BN, + block input): csrc/conv_bb.hip keeps b.conv1 on chip and picks its bias
+    row by border class"""
+    net = _net(hw)
+    net.add(Conv("s", "input", 3, planes, act="relu", **KW))
+    net.add(Conv("b.conv1", "s", planes, planes, act="prelu", pre_bn=True, **BN))
+    net.add(Conv("b.conv2", "b.conv1", planes, planes, res="s", **BN))
+    net.outputs = ["s", "b.conv2"]
+    layers = {"s": dict(density=1.0 / 3.0), "b.conv1": dict(density=8.0 / planes, mags=(1,), slopes=(0.5,)),
+              "b.conv2": dict(density=1.0, mags=(1, 2, 3))}
+    return _bn_probe(f"ir-{hw[0]}x{hw[1]}-{planes}x{batch}", net, 31, layers, {}, int_images(15, batch, hw), ["b.conv2"], ["b.conv1"])
+
+
+def shortcut_bn_probe(hw, cin, cout, batch):
+    """the first block of an IResNet stage as it is: b.down (1x1 / stride 2 + BN), b.conv1 (BN - conv - BN - PReLU), b.conv2 (stride 2 + BN, + b.down).
+    As in shortcut_probe the absorbed form never rounds b.down."""
+    net, layers = _net(hw), {}
+    x = _front(net, cin, layers)
+    net.add(Conv("b.down", x, cin, cout, k=1, stride=2, pad=0, **BN))
+    net.add(Conv("b.conv1", x, cin, cout, act="prelu", pre_bn=True, **BN))
+    net.add(Conv("b.conv2", "b.conv1", cout, cout, stride=2, res="b.down", **BN))
+    net.outputs = [x, "b.conv1", "b.conv2"]
+    layers.update({"b.down": dict(density=8.0 / cin, mags=(1,)), "b.conv1": dict(density=8.0 / (9 * cin), mags=(1,))})
+    return _bn_probe(f"shortcutbn-{hw[0]}x{hw[1]}-{cin}-{cout}x{batch}", net, 33, layers, {}, int_images(16, batch, hw), ["b.conv2"], ["b.down"])
+
+
+def stem_bn_probe(hw, act, batch):
+    """stem_probe with IResNet's BatchNorms: one in front of and one behind the 3x3 conv on the stem's map, one behind the shortcut"""
+    net = _net(hw)
+    net.add(Conv("stem", "input", 3, 64, act=act, **KW))
+    net.add(Conv("b.down", "stem", 64, 64, k=1, stride=2, pad=0, **BN))
+    net.add(Conv("b.conv1", "stem", 64, 64, act=act, pre_bn=True, **BN))
+    net.outputs = ["b.down", "b.conv1"]
+    return _bn_probe(f"stembn-{hw[0]}x{hw[1]}-{act}x{batch}", net, 35, {"b.down": FINE, "b.conv1": DENSE}, {}, int_images(17, batch, hw),
+                     ["b.down", "b.conv1"], ["stem"])
+
+
+FAMILY_BN_SHAPES = FAMILY_SHAPES + TINY_SHAPES
+FAMILY_BN_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(family_bn_probe), *sh) for sh in FAMILY_BN_SHAPES + MOSAIC_SHAPES}
+IR_SHAPES = [sh for sh in BB_SHAPES if sh[1] == 64]
+IR_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(ir_probe), *sh) for sh in IR_SHAPES}
+SHORTCUT_BN_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(shortcut_bn_probe), *sh) for sh in SHORTCUT_SHAPES}
+STEM_BN_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(stem_bn_probe), *sh) for sh in STEM_SHAPES}
+BN_KEYS = sorted(list(FAMILY_BN_KEYS.values()) + list(IR_KEYS.values()) + list(SHORTCUT_BN_KEYS.values()) + list(STEM_BN_KEYS.values()))

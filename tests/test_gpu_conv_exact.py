@@ -6,8 +6,11 @@ module.  tests/test_exact_probe_cpu.py asserts the conditions of that on every p
 fused block alternates its walking direction).  The op's INPUT tensor is read back and compared first: a mismatch there is a finding about the
 layer in front, not about the probed variant.
 
-Left to their tolerance tests, because their lowering only exists with a BatchNorm node (whose scale cannot be an exact power of two): IResNet's
-"ir" form of the fused block and the border-class bias rows of any conv behind a BatchNorm."""
+The lowerings that only exist with a BatchNorm node are covered by the probes of exact_probe.BN_KEYS (BatchNorm with a zero running mean:
+power-of-two scales, integer shifts): the nine border-class bias rows of a conv behind a BatchNorm through every kernel family, IResNet's "ir"
+form of the fused block, the first block of a stage with its BatchNorms, the fused stem block with a BatchNorm on its second conv.
+test_exact_probe_cpu.py::test_bn_probe_lowers_to_ideal_constants shows that the device receives the constants the reference assumes.  Nonzero
+running means stay with the tolerance tests."""
 import numpy as np
 import pytest
 
@@ -89,6 +92,51 @@ def test_conv_stride2_exact(ctx, monkeypatch, code, shape):
         pytest.skip(f"family code {code} takes neither form of this stride-2 conv")
 
 
+# ---- a BatchNorm in front: nine border-class bias rows, the class decoded from each family's own tile coordinates ------------------------
+# c: BN - conv - BN - PReLU, r: BN - conv - BN + input.  The family shapes, a 3x5 map (13 of 15 pixels on the border, seven images side by side on
+# a STRIP tile) and the 7x7 MOSAIC shape (the edges of four images inside one tile).
+
+BN_RAN = {}               # (family code, shape) -> the border-class convs of the probe the forced variant ran
+
+
+def _family_bn(ctx, monkeypatch, code, shape):
+    from scrfd_arcface_facerecognition_amd import lower
+    if (code, shape) not in BN_RAN:
+        force_family(monkeypatch, code)
+
+        def low_ok(low):
+            flags = {nm: (int(r[0]), int(r[11]) & lower.CF_BORDER) for nm, r in zip(low.op_names, low.ops)}
+            assert flags["c"] == (lower.OP_CONV, lower.CF_BORDER) and flags["r"] == (lower.OP_CONV, lower.CF_BORDER), low.op_names
+        ran = run_probe(ctx, ep.FAMILY_BN_KEYS[shape], code, check_low=low_ok)       # equality first, whichever variant took the layers
+        BN_RAN[(code, shape)] = sorted(set(ran) & {"c", "r"})
+    return BN_RAN[(code, shape)]
+
+
+BN_CASES = [(c, sh) for c in sorted(FAMILIES) if c != 10 for sh in ep.FAMILY_BN_SHAPES] + [(c, sh) for c in (96, 97, 11) for sh in ep.MOSAIC_SHAPES]
+
+
+@pytest.mark.parametrize("code,shape", BN_CASES, ids=lambda v: str(v) if isinstance(v, int) else _shape_id(v))
+def test_conv_family_bn_exact(ctx, monkeypatch, code, shape):
+    if not _family_bn(ctx, monkeypatch, code, shape):
+        pytest.skip(f"family code {code} takes neither form of this conv")
+
+
+# FAMILIES rows the library never gives a border-class conv, and why.  Every other row must have run one at one shape at least.
+NEVER_BORDER = {
+    10: "conv_s2.hip takes stride-2 convs only; a BatchNorm in front of a padded conv is folded for stride 1 (lower.py fold_conv), and its DUAL form excludes CF_BORDER",
+}
+
+
+def test_every_family_ran_a_border_class_conv(ctx, monkeypatch):
+    ran = {}
+    for code, shape in BN_CASES:
+        ran.setdefault(code, {})[_shape_id(shape)] = _family_bn(ctx, monkeypatch, code, shape)
+    for code in sorted(ran):
+        print(f"border-class convs run by family code {code} ({FAMILIES[code]['name']}):", {k: v for k, v in ran[code].items() if v} or "none")
+    took = {code for code, by_shape in ran.items() if any(by_shape.values())}
+    assert set(FAMILIES) - took == set(NEVER_BORDER), sorted(set(FAMILIES) - took)
+
+
 # ---- fused ops: fused and unfused lowering, each exact against the reference and hence against each other --------------------------------
 
 def _kinds(low):
@@ -114,6 +162,21 @@ def test_fused_basic_block_exact(ctx, monkeypatch, fuse, shape):
 
     def low_ok(low):
         assert (_kinds(low).count(lower.OP_BBLOCK) == 1) == bool(fuse) and (len(low.ops) == 2) == bool(fuse), low.op_names
+    run_probe(ctx, key, check_low=low_ok)
+
+
+# IResNet's form of the block (BN - conv - BN - PReLU - conv - BN, + input; arcface_r50's stride-1 blocks on 64 channels): conv1's bias row by border class
+@pytest.mark.parametrize("fuse,shape", [(f, sh) for sh in ep.IR_SHAPES for f in (True, "v2", False)],
+                         ids=lambda v: v if isinstance(v, str) else (str(v) if isinstance(v, bool) else f"{v[0][0]}x{v[0][1]}-{v[1]}x{v[2]}"))
+def test_fused_ir_block_exact(ctx, monkeypatch, fuse, shape):
+    from scrfd_arcface_facerecognition_amd import lower
+    key = ep.IR_KEYS[shape]
+    _env(monkeypatch, key, FID_NO_BB_FUSE=None if fuse else "1", FID_BB_V="2" if fuse == "v2" else None)
+
+    def low_ok(low):
+        assert (_kinds(low).count(lower.OP_BBLOCK) == 1) == bool(fuse) and (len(low.ops) == 2) == bool(fuse), low.op_names
+        op = low.ops[low.op_names.index("b.conv2" if fuse else "b.conv1")]
+        assert int(op[0]) == (lower.OP_BBLOCK if fuse else lower.OP_CONV) and int(op[11]) & lower.CF_BORDER, low.op_names
     run_probe(ctx, key, check_low=low_ok)
 
 
@@ -171,6 +234,21 @@ def test_fused_stem_block_exact(ctx, monkeypatch, fuse, shape):
     run_probe(ctx, key, check_low=low_ok)
 
 
+# the same with IResNet's BatchNorms: nine bias rows for the conv on the stem's map, in the fused op or in the conv of its own
+@pytest.mark.parametrize("fuse", [True, False])
+@pytest.mark.parametrize("shape", ep.STEM_SHAPES, ids=lambda v: f"{v[0][0]}x{v[0][1]}-{v[1]}x{v[2]}")
+def test_fused_stem_block_bn_exact(ctx, monkeypatch, fuse, shape):
+    from scrfd_arcface_facerecognition_amd import lower
+    key = ep.STEM_BN_KEYS[shape]
+    _env(monkeypatch, key, FID_NO_STEMBLOCK_FUSE=None if fuse else "1")
+
+    def low_ok(low):
+        assert (int(low.ops[0][0]) == lower.OP_STEMBLOCK) == fuse and ("stem.even" in low.tensor_id) == fuse and ("stem" in low.tensor_id) != fuse
+        op = low.ops[low.op_names.index("b.conv1")]
+        assert int(op[0]) == (lower.OP_STEMBLOCK if fuse else lower.OP_CONV) and int(op[11]) & lower.CF_BORDER, low.op_names
+    run_probe(ctx, key, check_low=low_ok)
+
+
 # the block shortcut (2x2 average pool + 1x1 conv, the weights become quarters) in the stride-2 conv's launch (conv_s2.hip DUAL)
 @pytest.mark.parametrize("fuse", [True, False])
 @pytest.mark.parametrize("shape", ep.DUAL_SHAPES, ids=lambda v: f"{v[0][0]}x{v[0][1]}-{v[1]}x{v[2]}")
@@ -183,14 +261,27 @@ def test_fused_shortcut_stride2_exact(ctx, monkeypatch, fuse, shape):
     run_probe(ctx, key, check_low=low_ok)
 
 
-# the 1x1 / stride-2 shortcut conv as extra K-steps of the conv that adds it (a generation-12 pick; "fused_s2": inside conv_s2.hip, ns = 10), without the
-# BatchNorm IResNet puts in front of conv1.  Three runs: the first one tunes with the shortcut as its own op.
-@pytest.mark.parametrize("mode,shape", [("fused", ep.SHORTCUT_SHAPES[0]), ("fused", ep.SHORTCUT_SHAPES[1]), ("fused_s2", ep.SHORTCUT_SHAPES[1]),
-                                        ("plain", ep.SHORTCUT_SHAPES[0]), ("plain", ep.SHORTCUT_SHAPES[1])],
-                         ids=lambda v: v if isinstance(v, str) else f"{v[0][0]}x{v[0][1]}-{v[1]}-{v[2]}x{v[3]}")
+# the 1x1 / stride-2 shortcut conv as extra K-steps of the conv that adds it (a generation-12 pick; "fused_s2": inside conv_s2.hip, ns = 10): first without the
+# BatchNorms of IResNet's block, then with them.  Three runs: the first one tunes with the shortcut as its own op.
+SHORTCUT_CASES = dict(argvalues=[("fused", ep.SHORTCUT_SHAPES[0]), ("fused", ep.SHORTCUT_SHAPES[1]), ("fused_s2", ep.SHORTCUT_SHAPES[1]),
+                                 ("plain", ep.SHORTCUT_SHAPES[0]), ("plain", ep.SHORTCUT_SHAPES[1])],
+                      ids=lambda v: v if isinstance(v, str) else f"{v[0][0]}x{v[0][1]}-{v[1]}-{v[2]}x{v[3]}")
+
+
+@pytest.mark.parametrize("mode,shape", **SHORTCUT_CASES)
 def test_fused_shortcut_conv_exact(ctx, monkeypatch, mode, shape):
+    _shortcut_case(ctx, monkeypatch, ep.SHORTCUT_KEYS[shape], mode, border=False)
+
+
+# the block in its real form: a BatchNorm behind the shortcut and behind both convs, one in front of conv1 (nine bias rows)
+@pytest.mark.parametrize("mode,shape", **SHORTCUT_CASES)
+def test_fused_shortcut_conv_bn_exact(ctx, monkeypatch, mode, shape):
+    _shortcut_case(ctx, monkeypatch, ep.SHORTCUT_BN_KEYS[shape], mode, border=True)
+
+
+def _shortcut_case(ctx, monkeypatch, key, mode, border):
+    from scrfd_arcface_facerecognition_amd import lower
     from scrfd_arcface_facerecognition_amd.engine import CompiledNet
-    key = ep.SHORTCUT_KEYS[shape]
     _env(monkeypatch, key, FID_NO_SC_FUSE="1" if mode == "plain" else None, FID_FORCE_GEN=None if mode == "plain" else "12",
          FID_FORCE_NS="10" if mode == "fused_s2" else None)
     probe = ep.PROBES[key]()
@@ -198,6 +289,7 @@ def test_fused_shortcut_conv_exact(ctx, monkeypatch, mode, shape):
     cn = CompiledNet(ctx, probe.net, probe.P, max_batch=probe.batch)
     try:
         assert (sum(int(r[0]) == 2 and int(r[23]) > 0 for r in cn.low.ops) == 1) == (mode != "plain")
+        assert bool(int(cn.low.ops[cn.low.op_names.index("b.conv1")][11]) & lower.CF_BORDER) == border
         names = [nm for nm in probe.net.outputs if nm in own_data_tensors(cn.low)]
         assert names == probe.net.outputs
         got = []
