@@ -124,6 +124,23 @@ int fid_net_macs(fid_net *net, double *macs_per_image);
 int fid_letterbox(fid_ctx *ctx, const uint8_t *frames_dev, int B, int H, int W,
                   uint8_t *out_dev, int in_h, int in_w, double *det_scale);
 
+/* ---- mixed-size batches: the *_ragged forms of fid_letterbox, fid_scrfd_postprocess, fid_align_crops and fid_align_crops_packed.
+ * The reference does all of these per image (build_targets, main.py:78-105, calls detect() and the recogniser once per photo); here one
+ * call takes B images of B different sizes.  A mixed batch is ONE device allocation plus two HOST arrays:
+ *   hw      int32 [B,2]  H_b, W_b
+ *   offsets int64 [B]    image b is dense uint8 [H_b, W_b, 3] BGR, its first byte at frames_dev + offsets[b]
+ * frames_bytes is the size of the allocation: no byte at or beyond it is ever read.  Images may overlap or repeat; the offsets need
+ * no alignment.  Validation is all-or-nothing: H, W <= 0, offsets[b] < 0, offsets[b] + H*W*3 > frames_bytes or a letterbox with
+ * new_h == 0 or new_w == 0 return FID_E_INVALID with the image index in fid_last_error(), and nothing is enqueued.  The per-image
+ * geometry is computed on the host in double, as fid_letterbox / fid_scrfd_postprocess compute it, and travels to a device table
+ * the context owns, ordered on the context's stream: hw and offsets may be freed or overwritten as soon as a call returns, calls
+ * enqueued back to back each read their own table, and no call synchronises with the host.  Limits on B, slots and rows as in the
+ * uniform calls; one kernel launch per stage for the whole batch.
+ *
+ * fid_letterbox_ragged: reference models/scrfd.py:123-138 per image; out [B,in_h,in_w,3]; det_scale: host [B] (new_h_b / H_b), may be NULL. */
+int fid_letterbox_ragged(fid_ctx *ctx, const uint8_t *frames_dev, size_t frames_bytes, const int32_t *hw, const int64_t *offsets,
+                         int B, uint8_t *out_dev, int in_h, int in_w, double *det_scale);
+
 /* ---- SCRFD post-process: replaces the numpy code of reference models/scrfd.py:89-178,180-207
  * and utils/helpers.py:62-107 (threshold, distance2bbox/kps decode, sort, greedy NMS, max_num).
  * The 9 head tensors (scores, bbox, kps for strides 8/16/32) are given as strided views so both
@@ -140,6 +157,13 @@ int fid_scrfd_postprocess(fid_ctx *ctx, const float *const head_dev[9], const in
                           int in_h, int in_w, int num_anchors, int img_h, int img_w, float conf_thres,
                           float iou_thres, int max_num, int metric, float *det_dev, float *kps_dev,
                           int32_t *counts_dev, int cap);
+/* The same for a mixed-size batch: frame b is the letterbox of an H_b x W_b image (hw: host int32 [B,2]).  Reference
+ * models/scrfd.py:145-148 (the division by that image's det_scale) and :159-177 (max_num around that image's centre), which the reference
+ * runs per image; sort, NMS and the capacity report through fid_scrfd_check are those of fid_scrfd_postprocess. */
+int fid_scrfd_postprocess_ragged(fid_ctx *ctx, const float *const head_dev[9], const int32_t pix_stride[9],
+                                 const int32_t anc_stride[9], const int64_t batch_stride[9], int B, int in_h, int in_w,
+                                 int num_anchors, const int32_t *hw, float conf_thres, float iou_thres, int max_num, int metric,
+                                 float *det_dev, float *kps_dev, int32_t *counts_dev, int cap);
 /* candidates per frame the sort/NMS workspace is sized for (default 4096; max 16800 = all anchors
  * of a 640x640 input) */
 int fid_scrfd_set_candidate_capacity(fid_ctx *ctx, int cand_cap);
@@ -170,6 +194,11 @@ int fid_align_crops(fid_ctx *ctx, const uint8_t *frames_dev, int B, int H, int W
                     const float *kps_dev, const int32_t *counts_dev, int cap, int faces_per_frame,
                     uint8_t *crops_dev, double *M_dev);
 
+/* The same for a mixed-size batch (reference utils/helpers.py:18-59, called per image): frame b is image b of the allocation; every
+ * slot gets exactly the crop and M row fid_align_crops writes when called for that image alone. */
+int fid_align_crops_ragged(fid_ctx *ctx, const uint8_t *frames_dev, size_t frames_bytes, const int32_t *hw, const int64_t *offsets, int B,
+                           const float *kps_dev, const int32_t *counts_dev, int cap, int faces_per_frame, uint8_t *crops_dev, double *M_dev);
+
 /* ---- packed face lists: every detected face of a batch as ONE dense row table, no per-frame padding.  The reference embeds every
  * face detect() returns (main.py:130-134: `detect(frame, params.max_num)` then `recognizer(frame, kps)` per face) and its default
  * max_num = 0 returns every NMS survivor (models/scrfd.py:159-177 selects only when max_num > 0); a B x faces_per_frame slot grid
@@ -187,6 +216,11 @@ int fid_face_pack(fid_ctx *ctx, const int32_t *counts_dev, int B, int cap, int m
  * crops: uint8 [n_rows,112,112,3]; M_dev (optional, may be NULL): [n_rows, 6].  n_rows <= 65535. */
 int fid_align_crops_packed(fid_ctx *ctx, const uint8_t *frames_dev, int B, int H, int W, const float *kps_dev, int cap,
                            const int32_t *src_dev, int n_rows, uint8_t *crops_dev, double *M_dev);
+
+/* The row-table form for a mixed-size batch (the warp is reference utils/helpers.py:18-59, per image there): row i gets exactly the crop
+ * and M row fid_align_crops_ragged writes for face f of frame b, src[i] = b*cap+f. */
+int fid_align_crops_packed_ragged(fid_ctx *ctx, const uint8_t *frames_dev, size_t frames_bytes, const int32_t *hw, const int64_t *offsets,
+                                  int B, const float *kps_dev, int cap, const int32_t *src_dev, int n_rows, uint8_t *crops_dev, double *M_dev);
 
 /* ---- face gates of the reference's product layer: replaces smart_face_recognition.py:1145-1216
  * (assess_face_quality), :1218-1297 (get_face_pose_angles / is_side_face), :1299-1399 (analyze_bbox_for_side_face) and the

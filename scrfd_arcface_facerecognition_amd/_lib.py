@@ -109,6 +109,13 @@ SIGNATURES = {
     "fid_net_macs": (C.c_int, [C.c_void_p, c_f64_p]),
     "fid_letterbox": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                 c_f64_p]),
+    "fid_letterbox_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, c_i32_p, c_i64_p, C.c_int, C.c_void_p, C.c_int, C.c_int, c_f64_p]),
+    "fid_scrfd_postprocess_ragged": (C.c_int, [C.c_void_p, c_void_pp, c_i32_p, c_i32_p, c_i64_p, C.c_int, C.c_int, C.c_int, C.c_int, c_i32_p,
+                                               C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "fid_align_crops_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, c_i32_p, c_i64_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_void_p]),
+    "fid_align_crops_packed_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, c_i32_p, c_i64_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_int, C.c_void_p, C.c_void_p]),
     "fid_scrfd_postprocess": (C.c_int, [C.c_void_p, c_void_pp, c_i32_p, c_i32_p, c_i64_p, C.c_int, C.c_int,
                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
@@ -202,6 +209,40 @@ def _ptr(x):
     return x
 
 
+def pack_images(images):
+    """A mixed-size batch as the *_ragged entry points take it (include/faceid.h): the images, each uint8 [H,W,3] with H, W >= 1, concatenated
+    in input order without padding.  -> (buffer uint8 1-D, hw int32 [B,2], offsets int64 [B]); pure numpy."""
+    images = list(images)
+    if not images:
+        raise ValueError("pack_images: no images")
+    hw = np.empty((len(images), 2), np.int32)
+    for i, im in enumerate(images):
+        shape, dtype = getattr(im, "shape", None), getattr(im, "dtype", None)
+        if dtype != np.uint8 or shape is None or len(shape) != 3 or shape[2] != 3 or shape[0] < 1 or shape[1] < 1:
+            raise ValueError(f"pack_images: image {i} is {dtype} {shape}, expected uint8 [H,W,3] with H, W >= 1")
+        hw[i] = shape[:2]
+    sizes = hw[:, 0].astype(np.int64) * hw[:, 1].astype(np.int64) * 3
+    offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+    buf = np.empty(int(sizes.sum()), np.uint8)
+    for im, o, n in zip(images, offsets, sizes):
+        buf[o:o + n] = np.asarray(im).reshape(-1)
+    return buf, hw, offsets
+
+
+class ImageBatch:
+    """A mixed-size batch on the device (Context.image_batch): `.frames` the one allocation, `.hw` / `.offsets` the host arrays the
+    *_ragged entry points read, `.nbytes` the allocation's size, `.B` the number of images.  `.args()` = the four leading arguments
+    (frames_dev, frames_bytes, hw, offsets) of those entry points."""
+
+    def __init__(self, ctx: "Context", images):
+        buf, self.hw, self.offsets = pack_images(images)
+        self.frames = ctx.to_device(buf)
+        self.nbytes, self.B = int(buf.nbytes), len(self.hw)
+
+    def args(self):
+        return (C.c_void_p(self.frames.ptr), C.c_size_t(self.nbytes), self.hw.ctypes.data_as(c_i32_p), self.offsets.ctypes.data_as(c_i64_p))
+
+
 class DeviceBuffer:
     """A typed view of device memory owned by the library's allocator (or borrowed)."""
 
@@ -274,6 +315,10 @@ class Context:
     def to_device(self, arr) -> DeviceBuffer:
         arr = np.ascontiguousarray(arr)
         return DeviceBuffer(self, arr.shape, arr.dtype).upload(arr)
+
+    def image_batch(self, images) -> ImageBatch:
+        """images of differing sizes, uploaded once as one allocation (pack_images)"""
+        return ImageBatch(self, images)
 
     def borrow(self, ptr, shape, dtype) -> DeviceBuffer:
         return DeviceBuffer(self, shape, dtype, ptr=ptr)

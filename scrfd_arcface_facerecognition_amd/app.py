@@ -90,28 +90,35 @@ class FaceAnalysis:
                      is_side_face=bool(side_flag[0, i]), side_face_score=int(side_score[0, i])) for i in range(n)]
 
     def get_batch(self, images, max_num: int = 0) -> List[List[Face]]:
-        """get() for a batch of images of ONE shape ([B,H,W,3] or a list): the detector runs on the batch (`SCRFD.detect_batch`, in its
+        """get() for a batch of images ([B,H,W,3], or a list whose images may differ in size: then every chunk is one mixed-size batch,
+        fid_align_crops_packed_ragged in place of fid_align_crops_packed): the detector runs on the batch (`SCRFD.detect_batch`, in its
         chunks of `max_batch` images), and all faces of a chunk's images -- every one, the reference's max_num = 0 default, or its
         top-`max_num` per image -- go through alignment, recogniser and normalisation as one packed row list (fid_face_pack), in runs of
         at most `max_faces` rows: nothing is truncated.  Gates: `face_gates` on the chunk's detections.  -> per image its list of Face."""
-        images = np.ascontiguousarray(np.stack([np.asarray(im, dtype=np.uint8) for im in images]) if isinstance(images, (list, tuple)) else images,
-                                      dtype=np.uint8)
-        assert images.ndim == 4 and images.shape[3] == 3, images.shape
+        mixed = isinstance(images, (list, tuple)) and len({tuple(np.shape(im)) for im in images}) > 1
+        if mixed:
+            images = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+        else:
+            images = np.ascontiguousarray(np.stack([np.asarray(im, dtype=np.uint8) for im in images]) if isinstance(images, (list, tuple)) else images,
+                                          dtype=np.uint8)
+            assert images.ndim == 4 and images.shape[3] == 3, images.shape
+            H, W = images.shape[1:3]
         ctx, lib = self.ctx, self.ctx.lib
-        H, W = images.shape[1:3]
         net = self.rec.session.compiled()
         out: List[List[Face]] = []
         step = self.det._max_batch
-        for b0 in range(0, images.shape[0], step):
+        for b0 in range(0, len(images), step):
             chunk = images[b0:b0 + step]
-            B = chunk.shape[0]
-            dets = self.det._detect_chunk(chunk, max_num, "max")        # host results; the post-process's device arrays stay valid
+            B = len(chunk)
+            batch = ctx.image_batch(chunk) if mixed else None
+            dets = (self.det._detect_chunk_ragged(chunk, max_num, "max", batch) if mixed
+                    else self.det._detect_chunk(chunk, max_num, "max"))   # host results; the post-process's device arrays stay valid
             post = self.det._postprocessor()
             total = sum(len(d) for d, _ in dets)
             if total == 0:
                 out += [[] for _ in range(B)]
                 continue
-            fr = ctx.to_device(chunk)
+            fr = None if mixed else ctx.to_device(chunk)
             offsets, src = ctx.empty((B + 1,), np.int32), ctx.empty((total,), np.int32)
             check(lib.fid_face_pack(ctx.handle, C.c_void_p(post.counts.ptr), B, post.cap, 0, C.c_void_p(offsets.ptr), C.c_void_p(src.ptr), total))
             emb = np.empty((total, 512), np.float32)
@@ -121,8 +128,12 @@ class FaceAnalysis:
             for r0 in range(0, total, self.max_faces):
                 n = min(self.max_faces, total - r0)
                 src_n = C.c_void_p(src.ptr + 4 * r0)
-                check(lib.fid_align_crops_packed(ctx.handle, C.c_void_p(fr.ptr), B, H, W, C.c_void_p(post.kps.ptr), post.cap, src_n, n,
-                                                 C.c_void_p(crops.ptr), None))
+                if mixed:
+                    check(lib.fid_align_crops_packed_ragged(ctx.handle, *batch.args(), B, C.c_void_p(post.kps.ptr), post.cap, src_n, n,
+                                                            C.c_void_p(crops.ptr), None))
+                else:
+                    check(lib.fid_align_crops_packed(ctx.handle, C.c_void_p(fr.ptr), B, H, W, C.c_void_p(post.kps.ptr), post.cap, src_n, n,
+                                                     C.c_void_p(crops.ptr), None))
                 net.run_device(crops, n)
                 emb_ptr, _, _ = net.tensor(net.low.outputs[0])
                 check(lib.fid_l2_normalize_f16_packed(ctx.handle, C.c_void_p(emb_ptr), n, 512, src_n, C.c_void_p(q.ptr)))

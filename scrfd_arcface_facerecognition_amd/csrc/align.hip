@@ -115,15 +115,33 @@ __global__ void __launch_bounds__(256) align_warp_packed(const uint8_t *frames, 
                     crops + (size_t)row * OUT * OUT * 3, M_out ? M_out + (size_t)row * 6 : nullptr, blockIdx.x * ROWS_PER_BLOCK);
 }
 
-// cv2.resize INTER_LINEAR u8 + zero letterbox paste (scrfd.py:135-138).
-__global__ void __launch_bounds__(256) letterbox_kernel(const uint8_t *frames, int H, int W, uint8_t *out, int in_h, int in_w,
-                                                        int new_h, int new_w, double scale_x, double scale_y, int area2x) {
-    const int b = blockIdx.z;
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= in_w) return;
-    uint8_t *o = out + (((size_t)b * in_h + y) * in_w + x) * 3;
+// Mixed-size batches (fid_align_crops_ragged / fid_align_crops_packed_ragged): the same two kernels with frame b's base pointer and
+// H, W read from the per-image table (fid::RaggedImg; block-uniform index, so the entry stays in scalar registers).
+__global__ void __launch_bounds__(256) align_warp_ragged(const uint8_t *frames, const fid::RaggedImg *tab, const float *kps, const int *counts,
+                                                         int cap, int F, uint8_t *crops, double *M_out) {
+    const int slot = blockIdx.y;  // b * F + f
+    const int b = slot / F, f = slot - b * F;
+    const bool valid = f < counts[b] && f < cap;
+    const fid::RaggedImg g = tab[b];
+    align_face_rows(frames + g.off, g.H, g.W, valid ? kps + ((size_t)b * cap + f) * 10 : nullptr,
+                    crops + (size_t)slot * OUT * OUT * 3, M_out ? M_out + (size_t)slot * 6 : nullptr, blockIdx.x * ROWS_PER_BLOCK);
+}
+
+__global__ void __launch_bounds__(256) align_warp_packed_ragged(const uint8_t *frames, const fid::RaggedImg *tab, int B, const float *kps, int cap,
+                                                                const int *src_rows, uint8_t *crops, double *M_out) {
+    const int row = blockIdx.y;
+    const int s = src_rows[row];
+    const bool valid = s >= 0 && s < B * cap;
+    const fid::RaggedImg g = tab[valid ? s / cap : 0];
+    align_face_rows(frames + g.off, g.H, g.W, valid ? kps + (size_t)s * 10 : nullptr,
+                    crops + (size_t)row * OUT * OUT * 3, M_out ? M_out + (size_t)row * 6 : nullptr, blockIdx.x * ROWS_PER_BLOCK);
+}
+
+// cv2.resize INTER_LINEAR u8 + zero letterbox paste (scrfd.py:135-138): output pixel (x, y) of one image, written to o.
+// Shared by the uniform and the mixed-size kernels: the two write the same bytes by construction.
+__device__ __forceinline__ void letterbox_pixel(const uint8_t *src, int H, int W, uint8_t *o, int x, int y, int new_h, int new_w,
+                                                double scale_x, double scale_y, int area2x) {
     if (x >= new_w || y >= new_h) { o[0] = o[1] = o[2] = 0; return; }
-    const uint8_t *src = frames + (size_t)b * H * W * 3;
     if (new_w == W && new_h == H) {
         const uint8_t *q = src + ((size_t)y * W + x) * 3;
         o[0] = q[0]; o[1] = q[1]; o[2] = q[2];
@@ -158,17 +176,33 @@ __global__ void __launch_bounds__(256) letterbox_kernel(const uint8_t *frames, i
     }
 }
 
+__global__ void __launch_bounds__(256) letterbox_kernel(const uint8_t *frames, int H, int W, uint8_t *out, int in_h, int in_w,
+                                                        int new_h, int new_w, double scale_x, double scale_y, int area2x) {
+    const int b = blockIdx.z;
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= in_w) return;
+    letterbox_pixel(frames + (size_t)b * H * W * 3, H, W, out + (((size_t)b * in_h + y) * in_w + x) * 3, x, y, new_h, new_w, scale_x, scale_y,
+                    area2x);
+}
+
+// a mixed-size batch: image blockIdx.z's geometry comes from the table; identity and exact-2x are decided per image
+__global__ void __launch_bounds__(256) letterbox_kernel_ragged(const uint8_t *frames, const fid::RaggedImg *tab, uint8_t *out, int in_h, int in_w) {
+    const int b = blockIdx.z;
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= in_w) return;
+    const fid::RaggedImg g = tab[b];
+    letterbox_pixel(frames + g.off, g.H, g.W, out + (((size_t)b * in_h + y) * in_w + x) * 3, x, y, g.new_h, g.new_w, g.scale_x, g.scale_y,
+                    g.mode == 2);
+}
+
 // The same arithmetic, FOUR consecutive output pixels per thread (in_w % 4 == 0): a source pixel is one unaligned 4-byte load instead of three
 // 1-byte loads and the 12 output bytes leave as three aligned dwords -- 16 + 3 memory instructions per 4 pixels instead of 48 + 12 (32 frames of
 // 1080p -> 640x640: cfg 5 step 1.548 -> 1.535 ms).  `src_bytes` = bytes of the whole frame batch: the last pixel of the batch is read bytewise.
-__global__ void __launch_bounds__(256) letterbox_kernel4(const uint8_t *frames, int H, int W, uint8_t *out, int in_h, int in_w, int new_h, int new_w,
-                                                         double scale_x, double scale_y, size_t src_bytes) {
-    const int b = blockIdx.z;
-    const int x4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, y = blockIdx.y;
-    if (x4 >= in_w) return;
-    unsigned *o = (unsigned *)(out + (((size_t)b * in_h + y) * in_w + x4) * 3);
+// Shared by the uniform and the mixed-size kernel, like letterbox_pixel.
+// letterbox_pixels4: output pixels x4 .. x4+3 of row y of the image whose first byte is frames[fbase], as three dwords at o.
+__device__ __forceinline__ void letterbox_pixels4(const uint8_t *frames, size_t fbase, int H, int W, unsigned *o, int x4, int y, int new_h, int new_w,
+                                                  double scale_x, double scale_y, size_t src_bytes) {
     unsigned char px[12];
-    const size_t fbase = (size_t)b * H * W * 3;
     auto fetch = [&](size_t off) -> unsigned {                  // the 3 bytes of a source pixel (byte 3 of the word is ignored)
         if (off + 4 <= src_bytes) {
             unsigned v;
@@ -208,6 +242,52 @@ __global__ void __launch_bounds__(256) letterbox_kernel4(const uint8_t *frames, 
 #pragma unroll
     for (int j = 0; j < 3; j++)
         o[j] = (unsigned)px[4 * j] | ((unsigned)px[4 * j + 1] << 8) | ((unsigned)px[4 * j + 2] << 16) | ((unsigned)px[4 * j + 3] << 24);
+}
+
+__global__ void __launch_bounds__(256) letterbox_kernel4(const uint8_t *frames, int H, int W, uint8_t *out, int in_h, int in_w, int new_h, int new_w,
+                                                         double scale_x, double scale_y, size_t src_bytes) {
+    const int b = blockIdx.z;
+    const int x4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, y = blockIdx.y;
+    if (x4 >= in_w) return;
+    letterbox_pixels4(frames, (size_t)b * H * W * 3, H, W, (unsigned *)(out + (((size_t)b * in_h + y) * in_w + x4) * 3), x4, y, new_h, new_w,
+                      scale_x, scale_y, src_bytes);
+}
+
+// a mixed-size batch, four pixels per thread; `src_bytes` = bytes of the caller's whole allocation (the guard of the 4-byte fetch).  An image
+// that is copied (identity) or decimated by exactly 2 (INTER_AREA) takes letterbox_pixel for its four pixels: the branch is block-uniform.
+__global__ void __launch_bounds__(256) letterbox_kernel4_ragged(const uint8_t *frames, const fid::RaggedImg *tab, uint8_t *out, int in_h, int in_w,
+                                                                size_t src_bytes) {
+    const int b = blockIdx.z;
+    const int x4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, y = blockIdx.y;
+    if (x4 >= in_w) return;
+    const fid::RaggedImg g = tab[b];
+    uint8_t *o = out + (((size_t)b * in_h + y) * in_w + x4) * 3;
+    if (g.mode != 0) {
+        for (int i = 0; i < 4; i++)
+            letterbox_pixel(frames + g.off, g.H, g.W, o + 3 * i, x4 + i, y, g.new_h, g.new_w, g.scale_x, g.scale_y, g.mode == 2);
+        return;
+    }
+    letterbox_pixels4(frames, (size_t)g.off, g.H, g.W, (unsigned *)o, x4, y, g.new_h, g.new_w, g.scale_x, g.scale_y, src_bytes);
+}
+
+// Host half of the mixed-size entry points: validate every image and compute its table entry (all-or-nothing: the caller enqueues nothing
+// when this fails).  in_h = 0: no letterbox (the warp needs only the base pointer and H, W).
+int ragged_entries(const int32_t *hw, const int64_t *offsets, size_t frames_bytes, int B, int in_h, int in_w, std::vector<fid::RaggedImg> &tab) {
+    tab.resize(B);
+    for (int b = 0; b < B; b++) {
+        const int H = hw[2 * b], W = hw[2 * b + 1];
+        FID_REQUIRE(H > 0 && W > 0, "image %d: bad size %dx%d", b, W, H);
+        const unsigned long long bytes = (unsigned long long)H * (unsigned long long)W * 3ull;
+        FID_REQUIRE(offsets[b] >= 0 && (unsigned long long)offsets[b] <= frames_bytes && bytes <= frames_bytes - (unsigned long long)offsets[b],
+                    "image %d: bytes [%lld, %lld + %llu) leave the allocation of %zu bytes", b, (long long)offsets[b], (long long)offsets[b], bytes,
+                    frames_bytes);
+        fid::RaggedImg g{};
+        if (in_h > 0) FID_REQUIRE(fid::ragged_geometry(H, W, in_h, in_w, &g), "image %d: degenerate letterbox %dx%d", b, g.new_w, g.new_h);
+        else { g.H = H; g.W = W; }
+        g.off = offsets[b];
+        tab[b] = g;
+    }
+    return FID_OK;
 }
 
 }  // namespace
@@ -267,6 +347,67 @@ int fid_letterbox(fid_ctx *ctx, const uint8_t *frames_dev, int B, int H, int W, 
     }
     hipLaunchKernelGGL(letterbox_kernel, grid, dim3(256), 0, ctx->stream, frames_dev, H, W, out_dev, in_h, in_w, new_h, new_w,
                        (double)W / (double)new_w, (double)H / (double)new_h, area2x);
+    FID_HIP(hipGetLastError());
+    return FID_OK;
+}
+
+// ---- mixed-size batches: image b is dense uint8 [H_b, W_b, 3] at frames_dev + offsets[b] (the reference runs all of these per image) ----
+int fid_letterbox_ragged(fid_ctx *ctx, const uint8_t *frames_dev, size_t frames_bytes, const int32_t *hw, const int64_t *offsets, int B,
+                         uint8_t *out_dev, int in_h, int in_w, double *det_scale) {
+    FID_REQUIRE(ctx && frames_dev && hw && offsets && out_dev, "NULL argument");
+    FID_REQUIRE(B > 0 && in_h > 0 && in_w > 0 && B <= 65535 && in_h <= 65535, "bad sizes");
+    std::vector<fid::RaggedImg> host;
+    FID_TRY(ragged_entries(hw, offsets, frames_bytes, B, in_h, in_w, host));
+    if (det_scale)
+        for (int b = 0; b < B; b++) det_scale[b] = (double)host[b].new_h / (double)host[b].H;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
+    const fid::RaggedImg *tab;
+    FID_TRY(fid::ragged_table(ctx, host.data(), B, &tab));
+    static const bool lb_bytes = getenv("FID_LETTERBOX_BYTES") != nullptr;      // A/B: the one-pixel-per-thread kernel everywhere
+    if (!lb_bytes && in_w % 4 == 0 && ((size_t)out_dev & 3) == 0) {
+        dim3 grid4(fid::cdiv(in_w / 4, 256), in_h, B);
+        hipLaunchKernelGGL(letterbox_kernel4_ragged, grid4, dim3(256), 0, ctx->stream, frames_dev, tab, out_dev, in_h, in_w, frames_bytes);
+    } else {
+        dim3 grid(fid::cdiv(in_w, 256), in_h, B);
+        hipLaunchKernelGGL(letterbox_kernel_ragged, grid, dim3(256), 0, ctx->stream, frames_dev, tab, out_dev, in_h, in_w);
+    }
+    FID_HIP(hipGetLastError());
+    return FID_OK;
+}
+
+int fid_align_crops_ragged(fid_ctx *ctx, const uint8_t *frames_dev, size_t frames_bytes, const int32_t *hw, const int64_t *offsets, int B,
+                           const float *kps_dev, const int32_t *counts_dev, int cap, int faces_per_frame, uint8_t *crops_dev, double *M_dev) {
+    FID_REQUIRE(ctx && frames_dev && hw && offsets && kps_dev && counts_dev && crops_dev, "NULL argument");
+    FID_REQUIRE(B > 0 && cap > 0 && faces_per_frame > 0, "bad sizes");
+    FID_REQUIRE((long long)B * faces_per_frame <= 65535, "too many face slots per call (%lld)", (long long)B * faces_per_frame);
+    std::vector<fid::RaggedImg> host;
+    FID_TRY(ragged_entries(hw, offsets, frames_bytes, B, 0, 0, host));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
+    const fid::RaggedImg *tab;
+    FID_TRY(fid::ragged_table(ctx, host.data(), B, &tab));
+    dim3 grid(OUT / ROWS_PER_BLOCK, B * faces_per_frame);
+    hipLaunchKernelGGL(align_warp_ragged, grid, dim3(256), 0, ctx->stream, frames_dev, tab, kps_dev, counts_dev, cap, faces_per_frame, crops_dev,
+                       M_dev);
+    FID_HIP(hipGetLastError());
+    return FID_OK;
+}
+
+int fid_align_crops_packed_ragged(fid_ctx *ctx, const uint8_t *frames_dev, size_t frames_bytes, const int32_t *hw, const int64_t *offsets, int B,
+                                  const float *kps_dev, int cap, const int32_t *src_dev, int n_rows, uint8_t *crops_dev, double *M_dev) {
+    FID_REQUIRE(ctx && frames_dev && hw && offsets && kps_dev && src_dev && crops_dev, "NULL argument");
+    FID_REQUIRE(B > 0 && cap > 0 && n_rows > 0, "bad sizes");
+    FID_REQUIRE((long long)B * cap <= 0x7FFFFFFFll, "B * cap = %lld overflows the row table's int32 entries", (long long)B * cap);
+    FID_REQUIRE(n_rows <= 65535, "too many face rows per call (%d)", n_rows);
+    std::vector<fid::RaggedImg> host;
+    FID_TRY(ragged_entries(hw, offsets, frames_bytes, B, 0, 0, host));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
+    const fid::RaggedImg *tab;
+    FID_TRY(fid::ragged_table(ctx, host.data(), B, &tab));
+    dim3 grid(OUT / ROWS_PER_BLOCK, n_rows);
+    hipLaunchKernelGGL(align_warp_packed_ragged, grid, dim3(256), 0, ctx->stream, frames_dev, tab, B, kps_dev, cap, src_dev, crops_dev, M_dev);
     FID_HIP(hipGetLastError());
     return FID_OK;
 }

@@ -92,6 +92,9 @@ struct fid_ctx {
     int cand_cap = 4096;
     int32_t *status_dev = nullptr;  // [0] max candidates seen, [1] max survivors seen
     int last_out_cap = 0;
+    // per-image geometry table of the *_ragged entry points (fid::ragged_table): grows, never shrinks
+    void *ragged_tab = nullptr;
+    int ragged_tab_cap = 0;         // entries
 };
 
 namespace fid {
@@ -103,4 +106,33 @@ int release_scratch(fid_ctx *ctx, int slot);
 // largest value set so far is remembered per (kernel, device) -- under a mutex: contexts on several devices and several host
 // threads launch the same kernels (a function-local static flag covered neither).
 int ensure_dyn_lds(fid_ctx *ctx, const void *func, int bytes);
+
+// One image of a mixed-size batch (the *_ragged entry points): where it lies in the caller's allocation and the letterbox geometry the
+// host computed for it in double (reference models/scrfd.py:123-138).  Every stage reads the entry of its image by a block-uniform index.
+struct RaggedImg {
+    long long off;              // first byte of the image, relative to frames_dev
+    int H, W;                   // the image
+    int new_h, new_w;           // resized size inside the letterbox
+    double scale_x, scale_y;    // W / new_w, H / new_h
+    float det_scale;            // (float)(new_h / H): what the post-process divides by
+    int mode;                   // letterbox: 0 bilinear, 1 identity copy, 2 exact 2x decimation (INTER_AREA)
+};
+static_assert(sizeof(RaggedImg) == 48, "RaggedImg is copied to the device as 48-byte entries");
+// letterbox geometry of one H x W image into in_h x in_w (scrfd.py:125-134 in double, int() truncation); false = degenerate
+inline bool ragged_geometry(int H, int W, int in_h, int in_w, RaggedImg *g) {
+    const double im_ratio = (double)H / (double)W, model_ratio = (double)in_h / (double)in_w;
+    int new_h, new_w;
+    if (im_ratio > model_ratio) { new_h = in_h; new_w = (int)((double)new_h / im_ratio); }
+    else { new_w = in_w; new_h = (int)((double)new_w * im_ratio); }
+    g->H = H; g->W = W; g->new_h = new_h; g->new_w = new_w;
+    if (new_h <= 0 || new_w <= 0) return false;
+    g->scale_x = (double)W / (double)new_w; g->scale_y = (double)H / (double)new_h;
+    g->det_scale = (float)((double)new_h / (double)H);
+    g->mode = (new_w == W && new_h == H) ? 1 : ((W == 2 * new_w && H == 2 * new_h) ? 2 : 0);
+    return true;
+}
+// Copy B host entries into the context's device table, ordered on the context's stream: the entries travel as kernel arguments of
+// small store kernels, so the host array is free when this returns, the write runs after every earlier reader of the table, and
+// nothing synchronises with the host (the table only reallocates, behind a stream synchronise, when B outgrows it).
+int ragged_table(fid_ctx *ctx, const RaggedImg *host, int B, const RaggedImg **dev);
 }  // namespace fid

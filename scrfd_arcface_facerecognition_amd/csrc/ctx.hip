@@ -1,6 +1,7 @@
 // Context, device memory, events.  Plain HIP runtime calls; no torch anywhere in this library.
 #include "common.h"
 
+#include <algorithm>
 #include <map>
 
 namespace fid {
@@ -55,6 +56,36 @@ int ensure_dyn_lds(fid_ctx *ctx, const void *func, int bytes) {
     }
     return FID_OK;
 }
+// ---- the per-image table of the mixed-size entry points ----
+constexpr int RAGGED_CHUNK = 64;              // entries per store kernel: 64 x 48 B = 3 KB of the 4 KB a kernel's arguments may take
+struct RaggedChunk { RaggedImg e[RAGGED_CHUNK]; };
+__global__ void __launch_bounds__(RAGGED_CHUNK) ragged_table_store(RaggedChunk c, int n, RaggedImg *dst) {
+    if ((int)threadIdx.x < n) dst[threadIdx.x] = c.e[threadIdx.x];
+}
+int ragged_table(fid_ctx *ctx, const RaggedImg *host, int B, const RaggedImg **dev) {
+    if (ctx->ragged_tab_cap < B) {
+        if (ctx->ragged_tab) {
+            FID_HIP(hipStreamSynchronize(ctx->stream));
+            FID_HIP(hipFree(ctx->ragged_tab));
+            ctx->ragged_tab = nullptr;
+            ctx->ragged_tab_cap = 0;
+        }
+        const int want = std::max(1024, B + B / 4);
+        FID_HIP(hipMalloc(&ctx->ragged_tab, (size_t)want * sizeof(RaggedImg)));
+        ctx->ragged_tab_cap = want;
+    }
+    RaggedImg *tab = (RaggedImg *)ctx->ragged_tab;
+    RaggedChunk c;
+    for (int b0 = 0; b0 < B; b0 += RAGGED_CHUNK) {
+        const int n = std::min(RAGGED_CHUNK, B - b0);
+        memcpy(c.e, host + b0, (size_t)n * sizeof(RaggedImg));
+        if (n < RAGGED_CHUNK) memset(c.e + n, 0, (size_t)(RAGGED_CHUNK - n) * sizeof(RaggedImg));
+        hipLaunchKernelGGL(ragged_table_store, dim3(1), dim3(RAGGED_CHUNK), 0, ctx->stream, c, n, tab + b0);
+    }
+    FID_HIP(hipGetLastError());
+    *dev = tab;
+    return FID_OK;
+}
 }  // namespace fid
 
 extern "C" {
@@ -103,6 +134,7 @@ int fid_ctx_destroy(fid_ctx *ctx) {
     for (int i = 0; i < FID_MAX_EVENTS; i++)
         if (ctx->events[i]) (void)hipEventDestroy(ctx->events[i]);
     if (ctx->status_dev) (void)hipFree(ctx->status_dev);
+    if (ctx->ragged_tab) (void)hipFree(ctx->ragged_tab);
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
     if (ctx->copy_done) (void)hipEventDestroy(ctx->copy_done);
     if (ctx->compute_done) (void)hipEventDestroy(ctx->compute_done);

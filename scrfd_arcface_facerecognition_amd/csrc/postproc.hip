@@ -27,11 +27,11 @@ __device__ __forceinline__ unsigned sortable(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-// One thread per anchor.  scrfd.py:89-119 + :145-148 (the division by det_scale).
-__global__ void __launch_bounds__(256) decode_compact(HeadViews hv, int in_h, int in_w, int A, float thr,
-                                                      float det_scale, int by_index, int cand_cap, int *cand_count,
-                                                      unsigned long long *cand_key, float *cand_data) {
-    const int b = blockIdx.y;
+// One thread per anchor.  scrfd.py:89-119 + :145-148 (the division by det_scale).  The body is shared by the uniform kernel and the
+// mixed-size one, which differ only in where frame b's det_scale comes from.
+__device__ __forceinline__ void decode_compact_frame(const HeadViews &hv, int b, int in_h, int in_w, int A, float thr, float det_scale,
+                                                     int by_index, int cand_cap, int *cand_count, unsigned long long *cand_key,
+                                                     float *cand_data) {
     const int n8 = (in_h / 8) * (in_w / 8) * A, n16 = (in_h / 16) * (in_w / 16) * A,
               n32 = (in_h / 32) * (in_w / 32) * A;
     int g = blockIdx.x * blockDim.x + threadIdx.x;  // flat anchor index over the 3 levels
@@ -67,6 +67,18 @@ __global__ void __launch_bounds__(256) decode_compact(HeadViews hv, int in_h, in
     // followed by nms()'s own stable argsort()[::-1] produces; identical to any order when tie-free)
     cand_key[(size_t)b * cand_cap + slot] =
         by_index ? ((unsigned long long)(~(unsigned)g) << 32) : (((unsigned long long)sortable(score) << 32) | (unsigned)(~(unsigned)g));
+}
+
+__global__ void __launch_bounds__(256) decode_compact(HeadViews hv, int in_h, int in_w, int A, float thr,
+                                                      float det_scale, int by_index, int cand_cap, int *cand_count,
+                                                      unsigned long long *cand_key, float *cand_data) {
+    decode_compact_frame(hv, blockIdx.y, in_h, in_w, A, thr, det_scale, by_index, cand_cap, cand_count, cand_key, cand_data);
+}
+
+// a mixed-size batch: frame b's det_scale from the per-image table (block-uniform)
+__global__ void __launch_bounds__(256) decode_compact_ragged(HeadViews hv, int in_h, int in_w, int A, float thr, const fid::RaggedImg *tab,
+                                                             int cand_cap, int *cand_count, unsigned long long *cand_key, float *cand_data) {
+    decode_compact_frame(hv, blockIdx.y, in_h, in_w, A, thr, tab[blockIdx.y].det_scale, 0, cand_cap, cand_count, cand_key, cand_data);
 }
 
 // distance2bbox / distance2kps on plain arrays (utils/helpers.py:62-107): ncol = 4 -> bbox, else kps pairs
@@ -123,12 +135,11 @@ constexpr int NMS_MASK_K = 512;   // candidate lists up to this length take the 
 // LDS: removed[cand_cap] bytes | keep[cand_cap] ints | value[cand_cap] floats | box[n_box] float4 | sup[NMS_MASK_K][NMS_MASK_K/32] masks.
 // The boxes of the n_box best candidates are staged in LDS: the greedy loop is one iteration + barrier per surviving candidate, and
 // reading candidate i's box from global memory put a trip to L2 (~0.3 us) on every iteration (29 us per 64-frame step).
-__global__ void __launch_bounds__(512) nms_select(const int *cand_count, const float *sorted, int cand_cap, float iou_thr,
-                                                  int max_num, int metric, int img_h, int img_w, float *det_out,
-                                                  float *kps_out, int *counts_out, int out_cap, int *keep_idx_out,
-                                                  int *status, int n_box, int mask_ok) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int b = blockIdx.x;
+// The body is shared by the uniform kernel and the mixed-size one, which differ only in where frame b's img_h, img_w come from.
+__device__ __forceinline__ void nms_select_frame(unsigned char *smem, int b, const int *cand_count, const float *sorted, int cand_cap,
+                                                 float iou_thr, int max_num, int metric, int img_h, int img_w, float *det_out,
+                                                 float *kps_out, int *counts_out, int out_cap, int *keep_idx_out,
+                                                 int *status, int n_box, int mask_ok) {
     const int Kraw = cand_count[b];
     const int K = min(Kraw, cand_cap);
     unsigned char *removed = smem;
@@ -256,6 +267,25 @@ __global__ void __launch_bounds__(512) nms_select(const int *cand_count, const f
     }
 }
 
+__global__ void __launch_bounds__(512) nms_select(const int *cand_count, const float *sorted, int cand_cap, float iou_thr,
+                                                  int max_num, int metric, int img_h, int img_w, float *det_out,
+                                                  float *kps_out, int *counts_out, int out_cap, int *keep_idx_out,
+                                                  int *status, int n_box, int mask_ok) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    nms_select_frame(smem, blockIdx.x, cand_count, sorted, cand_cap, iou_thr, max_num, metric, img_h, img_w, det_out, kps_out, counts_out,
+                     out_cap, keep_idx_out, status, n_box, mask_ok);
+}
+
+// a mixed-size batch: frame b's image size (the centre of the max_num metric, scrfd.py:169-172) from the per-image table
+__global__ void __launch_bounds__(512) nms_select_ragged(const int *cand_count, const float *sorted, int cand_cap, float iou_thr,
+                                                         int max_num, int metric, const fid::RaggedImg *tab, float *det_out,
+                                                         float *kps_out, int *counts_out, int out_cap, int *status, int n_box, int mask_ok) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const fid::RaggedImg g = tab[blockIdx.x];
+    nms_select_frame(smem, blockIdx.x, cand_count, sorted, cand_cap, iou_thr, max_num, metric, g.H, g.W, det_out, kps_out, counts_out,
+                     out_cap, (int *)nullptr, status, n_box, mask_ok);
+}
+
 }  // namespace
 
 namespace fid {
@@ -272,9 +302,10 @@ static size_t nms_lds_bytes(int cand_cap, int *n_box) {
     return base + (size_t)nb * 16 + (with_masks ? masks : 0);
 }
 // shared by fid_scrfd_postprocess and the fused pipeline
+// tab != NULL: a mixed-size batch -- det_scale and the image size of frame b come from tab[b], img_h / img_w are unused
 int scrfd_postprocess_launch(fid_ctx *ctx, const HeadViews &hv, int B, int in_h, int in_w, int A, int img_h, int img_w,
                              float conf, float iou, int max_num, int metric, float *det_dev, float *kps_dev,
-                             int32_t *counts_dev, int cap) {
+                             int32_t *counts_dev, int cap, const RaggedImg *tab = nullptr) {
     const int cc = ctx->cand_cap;
     // workspace: counts | keys | records | sorted records
     const size_t off_keys = ((size_t)B * 4 + 255) & ~(size_t)255;
@@ -297,14 +328,21 @@ int scrfd_postprocess_launch(fid_ctx *ctx, const HeadViews &hv, int B, int in_h,
     FID_HIP(hipMemsetAsync(cand_count, 0, (size_t)B * 4, ctx->stream));
     const int total_anchors = ((in_h / 8) * (in_w / 8) + (in_h / 16) * (in_w / 16) + (in_h / 32) * (in_w / 32)) * A;
     dim3 g1(cdiv(total_anchors, 256), B);
-    hipLaunchKernelGGL(decode_compact, g1, dim3(256), 0, ctx->stream, hv, in_h, in_w, A, conf, det_scale, 0, cc, cand_count,
-                       keys, data);
+    if (tab)
+        hipLaunchKernelGGL(decode_compact_ragged, g1, dim3(256), 0, ctx->stream, hv, in_h, in_w, A, conf, tab, cc, cand_count, keys, data);
+    else
+        hipLaunchKernelGGL(decode_compact, g1, dim3(256), 0, ctx->stream, hv, in_h, in_w, A, conf, det_scale, 0, cc, cand_count,
+                           keys, data);
     dim3 g2(cdiv(cc, 256), B);
     hipLaunchKernelGGL(rank_scatter, g2, dim3(256), 0, ctx->stream, cand_count, keys, data, sorted, cc);
     int n_box = 0;
     const size_t lds = nms_lds_bytes(cc, &n_box);
-    hipLaunchKernelGGL(nms_select, dim3(B), dim3(512), lds, ctx->stream, cand_count, sorted, cc, iou, max_num, metric, img_h,
-                       img_w, det_dev, kps_dev, counts_dev, cap, (int *)nullptr, ctx->status_dev, n_box < 0 ? -n_box : n_box, n_box > 0);
+    if (tab)
+        hipLaunchKernelGGL(nms_select_ragged, dim3(B), dim3(512), lds, ctx->stream, cand_count, sorted, cc, iou, max_num, metric, tab,
+                           det_dev, kps_dev, counts_dev, cap, ctx->status_dev, n_box < 0 ? -n_box : n_box, n_box > 0);
+    else
+        hipLaunchKernelGGL(nms_select, dim3(B), dim3(512), lds, ctx->stream, cand_count, sorted, cc, iou, max_num, metric, img_h,
+                           img_w, det_dev, kps_dev, counts_dev, cap, (int *)nullptr, ctx->status_dev, n_box < 0 ? -n_box : n_box, n_box > 0);
     FID_HIP(hipGetLastError());
     ctx->last_out_cap = cap;
     return FID_OK;
@@ -346,6 +384,40 @@ int fid_scrfd_postprocess(fid_ctx *ctx, const float *const head_dev[9], const in
     FID_TRY(fid::ensure_dyn_lds(ctx, (const void *)nms_select, (int)fid::nms_lds_bytes(ctx->cand_cap, nullptr)));   // (above 64 KB from ~2000 candidates on)
     return fid::scrfd_postprocess_launch(ctx, hv, B, in_h, in_w, num_anchors, img_h, img_w, conf_thres, iou_thres, max_num,
                                          metric, det_dev, kps_dev, counts_dev, cap);
+}
+
+// A mixed-size batch (the reference runs scrfd.py:145-148,159-177 per image): frame b came from an H_b x W_b image, hw = host [B,2].
+int fid_scrfd_postprocess_ragged(fid_ctx *ctx, const float *const head_dev[9], const int32_t pix_stride[9],
+                                 const int32_t anc_stride[9], const int64_t batch_stride[9], int B, int in_h, int in_w,
+                                 int num_anchors, const int32_t *hw, float conf_thres, float iou_thres, int max_num,
+                                 int metric, float *det_dev, float *kps_dev, int32_t *counts_dev, int cap) {
+    FID_REQUIRE(ctx && head_dev && pix_stride && anc_stride && batch_stride && hw, "NULL argument");
+    FID_REQUIRE(B > 0 && cap > 0 && det_dev && kps_dev && counts_dev, "bad batch/capacity/output");
+    FID_REQUIRE(in_h > 0 && in_w > 0 && in_h % 32 == 0 && in_w % 32 == 0, "input size %dx%d not a multiple of 32", in_w, in_h);
+    FID_REQUIRE(num_anchors > 0, "bad anchors");
+    FID_REQUIRE(metric == 0 || metric == 1, "metric must be 0 (max) or 1 (default)");
+    HeadViews hv;
+    for (int k = 0; k < 9; k++) {
+        FID_REQUIRE(head_dev[k], "head %d is NULL", k);
+        hv.ptr[k] = head_dev[k];
+        hv.pix_stride[k] = pix_stride[k];
+        hv.anc_stride[k] = anc_stride[k];
+        hv.batch_stride[k] = batch_stride[k];
+    }
+    std::vector<fid::RaggedImg> host(B);
+    for (int b = 0; b < B; b++) {
+        FID_REQUIRE(hw[2 * b] > 0 && hw[2 * b + 1] > 0, "image %d: bad size %dx%d", b, hw[2 * b + 1], hw[2 * b]);
+        FID_REQUIRE(fid::ragged_geometry(hw[2 * b], hw[2 * b + 1], in_h, in_w, &host[b]), "image %d: degenerate letterbox %dx%d", b,
+                    host[b].new_w, host[b].new_h);
+        host[b].off = 0;
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
+    FID_TRY(fid::ensure_dyn_lds(ctx, (const void *)nms_select_ragged, (int)fid::nms_lds_bytes(ctx->cand_cap, nullptr)));
+    const fid::RaggedImg *tab;
+    FID_TRY(fid::ragged_table(ctx, host.data(), B, &tab));
+    return fid::scrfd_postprocess_launch(ctx, hv, B, in_h, in_w, num_anchors, 1, 1, conf_thres, iou_thres, max_num, metric, det_dev,
+                                         kps_dev, counts_dev, cap, tab);
 }
 
 // SCRFD.forward's decode loop alone (scrfd.py:89-119): candidates >= threshold in anchor order

@@ -212,6 +212,16 @@ class PostProcessor:
             int(in_hw[1]), int(A), int(img_hw[0]), int(img_hw[1]), float(conf), float(iou), int(max_num),
             int(metric), C.c_void_p(self.det.ptr), C.c_void_p(self.kps.ptr), C.c_void_p(self.counts.ptr), self.cap))
 
+    def run_ragged(self, hv: HeadViews, B, in_hw, hw, conf, iou, max_num=0, metric=0, A=2):
+        """run() for a mixed-size batch: frame b is the letterbox of an hw[b] = (H_b, W_b) image (fid_scrfd_postprocess_ragged)"""
+        assert B <= self.max_batch
+        hw = np.ascontiguousarray(hw, dtype=np.int32).reshape(-1, 2)
+        assert len(hw) == B, (hw.shape, B)
+        check(self.ctx.lib.fid_scrfd_postprocess_ragged(
+            self.ctx.handle, C.cast(hv.ptrs, _lib.c_void_pp), hv.pix, hv.anc, hv.bstride, int(B), int(in_hw[0]),
+            int(in_hw[1]), int(A), hw.ctypes.data_as(_lib.c_i32_p), float(conf), float(iou), int(max_num),
+            int(metric), C.c_void_p(self.det.ptr), C.c_void_p(self.kps.ptr), C.c_void_p(self.counts.ptr), self.cap))
+
     def check(self) -> int:
         m = C.c_int()
         check(self.ctx.lib.fid_scrfd_check(self.ctx.handle, C.byref(m)))

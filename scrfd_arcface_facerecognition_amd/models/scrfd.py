@@ -89,7 +89,15 @@ class SCRFD:
         return scores_list, bboxes_list, kpss_list
 
     def detect_batch(self, images, max_num=0, metric="max") -> List[Tuple[np.ndarray, np.ndarray]]:
-        """Batched detect(): images uint8 [B,H,W,3] (one shape) -> [(det[K,5], kpss[K,5,2])] per frame."""
+        """Batched detect(): images uint8 [B,H,W,3], or a list of uint8 [H,W,3] images -> [(det[K,5], kpss[K,5,2])] per frame.
+        A list whose images differ in shape runs in chunks of `max_batch` consecutive images, each ONE mixed-size batch
+        (`_detect_chunk_ragged`); the reference detects such images one by one (main.py:96)."""
+        if isinstance(images, (list, tuple)) and len({tuple(np.shape(im)) for im in images}) > 1:
+            images = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+            results = []
+            for b0 in range(0, len(images), self._max_batch):
+                results += self._detect_chunk_ragged(images[b0:b0 + self._max_batch], max_num, metric)
+            return results
         images = np.ascontiguousarray(images, dtype=np.uint8)
         assert images.ndim == 4 and images.shape[3] == 3
         results = []
@@ -113,6 +121,20 @@ class SCRFD:
         post = self._postprocessor()
         post.run(HeadViews.from_fused(cn), B, (in_h, in_w), (H, W), self.conf_thres, self.iou_thres, max_num,
                  0 if metric == "max" else 1, self._num_anchors)
+        return post.fetch(B)
+
+    def _detect_chunk_ragged(self, images, max_num, metric, batch=None):
+        """_detect_chunk for images of differing sizes (at most max_batch): pack, letterbox, ONE net run and post-process for the whole
+        list.  `batch`: the list already on the device (Context.image_batch)."""
+        batch = self.ctx.image_batch(images) if batch is None else batch
+        B = batch.B
+        in_w, in_h = self.input_size
+        det_in = self.ctx.empty((B, in_h, in_w, 3), np.uint8)
+        check(self.ctx.lib.fid_letterbox_ragged(self.ctx.handle, *batch.args(), B, C.c_void_p(det_in.ptr), in_h, in_w, None))
+        cn = self._run_net(det_in, B, (in_h, in_w))
+        post = self._postprocessor()
+        post.run_ragged(HeadViews.from_fused(cn), B, (in_h, in_w), batch.hw, self.conf_thres, self.iou_thres, max_num,
+                        0 if metric == "max" else 1, self._num_anchors)
         return post.fetch(B)
 
     def detect(self, image, max_num=0, metric="max"):

@@ -432,8 +432,9 @@ def build_targets_from_images(detector, recognizer, images: Sequence[np.ndarray]
     per image `detect(image, max_num=1)` (:96), images without a face are skipped with a warning (:98-100),
     the best face is embedded (`recognizer(image, kpss[0])`, :102) and `(embedding, name)` collected (:103),
     in input order.  Images of one shape go through the detector, the alignment and the recogniser as ONE
-    batch each (detect_batch -> fid_align_crops -> get_feat); objects without the batched surface are driven
-    through the reference's per-image calls."""
+    batch (detect_batch -> fid_align_crops -> get_feat); images of differing shapes go through them in chunks of
+    the detector's `max_batch` consecutive images, each one mixed-size batch (fid_align_crops_ragged); objects
+    without the batched surface are driven through the reference's per-image calls."""
     import logging
     assert len(images) == len(names)
     kps_of: List[Optional[np.ndarray]] = [None] * len(images)
@@ -442,6 +443,27 @@ def build_targets_from_images(detector, recognizer, images: Sequence[np.ndarray]
     for i, im in enumerate(images):
         by_shape.setdefault(tuple(im.shape), []).append(i)
     emb_of: List[Optional[np.ndarray]] = [None] * len(images)
+    if batched and len(by_shape) > 1 and hasattr(detector, "_detect_chunk_ragged"):
+        ctx = recognizer.ctx
+        step = detector._max_batch
+        for b0 in range(0, len(images), step):
+            ids = list(range(b0, min(b0 + step, len(images))))
+            chunk = [np.ascontiguousarray(images[i], dtype=np.uint8) for i in ids]
+            dets = detector.detect_batch(chunk, max_num=1)
+            hit = [k for k, (_, kpss) in enumerate(dets) if len(kpss)]
+            if not hit:
+                continue
+            n = len(hit)
+            kps = np.stack([dets[k][1][0].reshape(10) for k in hit]).astype(np.float32).reshape(n, 1, 10)
+            batch = ctx.image_batch([chunk[k] for k in hit])
+            kp, cn = ctx.to_device(kps), ctx.to_device(np.ones(n, np.int32))
+            crops = ctx.empty((n, 112, 112, 3), np.uint8)
+            check(ctx.lib.fid_align_crops_ragged(ctx.handle, *batch.args(), n, C.c_void_p(kp.ptr), C.c_void_p(cn.ptr), 1, 1,
+                                                 C.c_void_p(crops.ptr), None))
+            feats = recognizer.get_feat(crops.download())
+            for k, e in zip(hit, feats):
+                emb_of[ids[k]] = np.ascontiguousarray(e, dtype=np.float32).reshape(-1)
+        by_shape = {}
     for shape, ids in by_shape.items():
         if not batched:
             for i in ids:
