@@ -284,6 +284,15 @@ int fid_gallery_data(fid_gallery *g, void **unit_rows_dev);
 int fid_gallery_topk(fid_ctx *ctx, fid_gallery *g, const void *query_f16_dev, int n, int k, float thresh,
                      int32_t *idx_dev, float *score_dev);
 int fid_gallery_set_rows(fid_ctx *ctx, fid_gallery *g, const int32_t *rows_host, const float *emb_host, int n);
+/* Range search / similarity join: every (query, gallery row) with cosine >= thresh (and > 0), not the best k -- what the product layer's
+ * duplicate merge asks of its vector store (reference smart_face_recognition.py:2761-2766: `search_similar(k=len(persons), threshold)`;
+ * qdrant_manager.py:137-183, whose score_threshold keeps scores >= the threshold).  A zero (deleted / free) row and a NaN never hit.
+ * query_f16_dev: unit fp16 [n, dim], or NULL = self-join (n is ignored; pairs i < j of the gallery's own rows, each once).
+ * pairs_dev int32 [hit_cap, 2] = (query, row); scores_dev float [hit_cap]; total_dev uint64 [1] = number of hits found,
+ * NOT clipped to hit_cap (total > hit_cap: hit_cap valid records, which ones is unspecified; call again with more room).
+ * Record order is unspecified; the set and the scores are deterministic.  Asynchronous; no host synchronisation. */
+int fid_gallery_range(fid_ctx *ctx, fid_gallery *g, const void *query_f16_dev, int n, float thresh,
+                      int32_t *pairs_dev, float *scores_dev, long long hit_cap, uint64_t *total_dev);
 /* Gallery sharded over ranks by contiguous row blocks (the 1 M-entry variant of main.py:136-142):
  * fid_match_keys scans THIS rank's rows (global index of its row 0 = first_row) for all n queries and writes one
  * packed key per query, (order-preserving bits of the score << 32) | ~global_index; after the ranks' key arrays

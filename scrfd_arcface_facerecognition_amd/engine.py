@@ -348,11 +348,58 @@ class VectorGallery:
             out[c0:c0 + len(blk)] = cm.download()[:len(blk), :gal.G]
         return out
 
-    def find_and_merge_duplicates(self, similarity_threshold: float = 0.8):
+    # ---- range search and self-join (fid_gallery_range): every hit at or above a threshold, only the records cross PCIe ------------------------
+    hit_capacity = 1 << 16          # records the first call of a range search has room for; a fuller answer is fetched by a second, larger call
+
+    def _range(self, q_ptr, n: int, threshold: float):
+        """fid_gallery_range with the grow-and-repeat contract -> (pairs int32 [total, 2], scores fp32 [total]) on the host"""
+        cap = max(1, int(self.hit_capacity))
+        total_dev = self.ctx.empty((1,), np.uint64)
+        while True:
+            pairs, scores = self.ctx.empty((cap, 2), np.int32), self.ctx.empty((cap,), np.float32)
+            check(self.ctx.lib.fid_gallery_range(self.ctx.handle, self._gal.handle, C.c_void_p(q_ptr), int(n), float(threshold),
+                                                 C.c_void_p(pairs.ptr), C.c_void_p(scores.ptr), cap, C.c_void_p(total_dev.ptr)))
+            total = int(total_dev.download()[0])
+            if total <= cap:
+                break
+            cap = total                                   # the counter is not clipped: it names the room the answer needs
+        if total == 0:
+            return np.empty((0, 2), np.int32), np.empty((0,), np.float32)
+        return (self.ctx.borrow(pairs.ptr, (total, 2), np.int32).download(), self.ctx.borrow(scores.ptr, (total,), np.float32).download())
+
+    def range_search(self, embeddings, score_threshold: float):
+        """-> per query a list of (id, score): EVERY stored embedding with score >= threshold (and > 0), best first, ascending row among equal
+        scores -- the reference's `search_similar(k=len(persons), threshold=...)` (smart_face_recognition.py:2761-2766)"""
+        emb = np.ascontiguousarray(embeddings, dtype=np.float32).reshape(-1, self.dim)
+        n = emb.shape[0]
+        e = self.ctx.to_device(emb)
+        q = self.ctx.empty((n, self.dim), np.float16)
+        check(self.ctx.lib.fid_l2_normalize_f16(self.ctx.handle, C.c_void_p(e.ptr), n, self.dim, C.c_void_p(q.ptr)))
+        pairs, scores = self._range(q.ptr, n, score_threshold)
+        out = [[] for _ in range(n)]
+        for k in np.lexsort((pairs[:, 1], -scores, pairs[:, 0])):
+            out[int(pairs[k, 0])].append((self.id_of[int(pairs[k, 1])], float(scores[k])))
+        return out
+
+    def similar_pairs(self, threshold: float):
+        """-> [(id_a, id_b, score)]: every pair of stored embeddings with score >= threshold (and > 0), each once with row_of[id_a] < row_of[id_b],
+        sorted by (row a, row b); the self-join of fid_gallery_range"""
+        pairs, scores = self._range(0, 0, threshold)
+        return [(self.id_of[int(pairs[k, 0])], self.id_of[int(pairs[k, 1])], float(scores[k])) for k in np.lexsort((pairs[:, 1], pairs[:, 0]))]
+
+    def find_and_merge_duplicates(self, similarity_threshold: float = 0.8, via: str = "matrix"):
         """The reference's `find_and_merge_duplicates` (smart_face_recognition.py:2726-2797; config.json `merge_duplicate_threshold`) on the vector
         store: ids in ascending order; every id that is still stored absorbs all LARGER ids whose similarity reaches the threshold (their rows are
         deleted, as merge_duplicate_persons does through delete_embedding).  The G x G similarities come from the device in one pass (deletions only
-        remove candidates, no embedding changes); the greedy pass over them is the reference's loop.  Returns [(kept id, deleted id, similarity)]."""
+        remove candidates, no embedding changes); the greedy pass over them is the reference's loop.  Returns [(kept id, deleted id, similarity)].
+        via="join": the same merges from the self-join's pair list (similar_pairs + merge_from_pairs) instead of the dense matrix."""
+        if via == "join":
+            merges = merge_from_pairs(list(self.row_of), self.similar_pairs(similarity_threshold), similarity_threshold)
+            if merges:
+                self.delete([m[1] for m in merges])
+            return merges
+        if via != "matrix":
+            raise ValueError(f"find_and_merge_duplicates: via={via!r}, expected 'matrix' or 'join'")
         ids = sorted(self.row_of)
         if len(ids) < 2:
             return []
@@ -375,6 +422,29 @@ class VectorGallery:
         if merges:
             self.delete([m[1] for m in merges])
         return merges
+
+
+def merge_from_pairs(ids, pairs, threshold: float):
+    """The reference's greedy merge loop (smart_face_recognition.py:2755-2792) on a pair list [(id_a, id_b, score)] (each unordered pair at most
+    once, either order): ids in ascending order; every id that is still alive absorbs each alive LARGER id it is paired with at score >= threshold,
+    its hits taken score-descending, then in ascending id order (what a stable argsort over the ascending ids gives).  Pure host code.
+    Returns [(kept id, deleted id, score)] in the order the merges happen."""
+    hits = {i: [] for i in ids}
+    for a, b, s in pairs:
+        if s >= threshold:
+            hits[a].append((b, s))
+            hits[b].append((a, s))
+    alive = set(hits)
+    merges = []
+    for p1 in sorted(hits):
+        if p1 not in alive:
+            continue
+        for p2, s in sorted(hits[p1], key=lambda h: (-h[1], h[0])):
+            if p2 <= p1 or p2 not in alive:
+                continue
+            alive.discard(p2)
+            merges.append((p1, p2, float(s)))
+    return merges
 
 
 def _gallery_ptr(gal: Gallery) -> int:
