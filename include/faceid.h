@@ -293,6 +293,40 @@ int fid_gallery_set_rows(fid_ctx *ctx, fid_gallery *g, const int32_t *rows_host,
  * Record order is unspecified; the set and the scores are deterministic.  Asynchronous; no host synchronisation. */
 int fid_gallery_range(fid_ctx *ctx, fid_gallery *g, const void *query_f16_dev, int n, float thresh,
                       int32_t *pairs_dev, float *scores_dev, long long hit_cap, uint64_t *total_dev);
+/* Grouping a batch of visits into persons, in visit order: the reference's process_visit_data loop (smart_face_recognition.py:1721-2005, per-visit
+ * body :1769-1951; the JSON twin :2077-2240 differs only in the threshold key) as ONE asynchronous call.  Per visit the reference runs
+ * is_duplicate_image (:2618-2652: k = 1 search at duplicate_similarity_threshold = dup_thresh; a hit skips the visit), search_person (:1619-1643:
+ * k = 5 at similarity_threshold = search_thresh), groups with the best hit when its similarity >= grouping_threshold_file / _json = group_thresh
+ * (:1859-1861) and otherwise add_person (:1531-1602), which stores the embedding (qdrant_manager.py:91-136).  Its serial order (max_workers = 1)
+ * is the one computed here.
+ * query_f16_dev: n unit fp16 rows in visit order, as fid_l2_normalize_f16* writes them (16-byte aligned).  new_rows_dev: int32 [n_new_rows] gallery
+ * rows the caller guarantees to be free (all zero) and distinct; the k-th NEW visit of the call is stored in new_rows[k].
+ * Visit i is decided against the store AS VISIT i SEES IT: every gallery row as it was at the call plus the rows written for NEW visits < i.
+ * best(i) = the maximum cosine over that store, lowest row among equal scores; a score that is not > 0 is no hit (score 0, row -1: the rule
+ * of fid_match / fid_gallery_topk).  Verdicts, checked in this order:
+ *   FID_VISIT_NO_FACE    the query row has no non-zero element (the all +0.0 row of a degenerate embedding, the -0.0-first marker row of an
+ *                        empty slot).  Nothing stored, row -1, score 0, never anybody's candidate -- also behind a DEFERRED visit.
+ *   FID_VISIT_DEFERRED   an earlier visit of this call needed a row when none of the n_new_rows was left: that visit and every (non-zero)
+ *                        visit after it are NOT decided and not stored (row -1, score 0).  The decided prefix is exactly what a call on
+ *                        that prefix alone returns; make room and call again with the suffix.
+ *   FID_VISIT_DUPLICATE  best.score >= dup_thresh (:2636-2645; Qdrant's score_threshold keeps >=).  Nothing stored; row, score = best.
+ *   FID_VISIT_RECOGNISED best.score >= search_thresh && best.score >= group_thresh (:1854-1861).  Nothing stored; row, score = best.
+ *   FID_VISIT_NEW        otherwise: the query's fp16 row is copied BIT FOR BIT into gallery row new_rows[k], k = number of NEW verdicts
+ *                        before it; row = that row; score = best.score if >= search_thresh else 0 (the `similarity` of :1855).
+ * Outputs (device): verdict int32 [n], row int32 [n], score float [n], summary int32 [2] = {number of NEW, index of the first DEFERRED visit
+ * or n}.  No gallery row outside new_rows[0 : summary[0]] is written.  An entry of new_rows outside [0, G) cannot be checked without a
+ * synchronise: the visit is still NEW and consumes the entry, but NOTHING is stored, its row reads -1 and it is nobody's candidate.
+ * Not here: the reference's "store is empty -> similarity 1.0" (:1820-1851; changes no decision -- engine.VectorGallery.group_visits reports
+ * it), the SQL URL checks and add_person's md5 face_hash (an identical embedding scores 1.0 and is a DUPLICATE already).
+ * FID_E_INVALID, nothing enqueued: a NULL pointer, n <= 0 or n > FID_GROUP_MAX_VISITS, n_new_rows < 0, a threshold that is NaN or <= 0
+ * (the "> 0" hit rule makes it meaningless), dim % 32 != 0.  Asynchronous on the context's stream.  It does not synchronise with the host,
+ * with the exception every entry point that uses a scratch arena shares (fid_match among them): the arena (1.3 MB here, sized for
+ * FID_GROUP_MAX_VISITS at the first call, shared with fid_match) is replaced behind a stream synchronise when a call needs a larger one. */
+enum { FID_VISIT_NEW = 0, FID_VISIT_RECOGNISED = 1, FID_VISIT_DUPLICATE = 2, FID_VISIT_NO_FACE = 3, FID_VISIT_DEFERRED = 4 };
+#define FID_GROUP_MAX_VISITS 65536
+int fid_gallery_group(fid_ctx *ctx, fid_gallery *g, const void *query_f16_dev, int n, float dup_thresh, float group_thresh,
+                      float search_thresh, const int32_t *new_rows_dev, int n_new_rows, int32_t *verdict_dev, int32_t *row_dev,
+                      float *score_dev, int32_t *summary_dev);
 /* Gallery sharded over ranks by contiguous row blocks (the 1 M-entry variant of main.py:136-142):
  * fid_match_keys scans THIS rank's rows (global index of its row 0 = first_row) for all n queries and writes one
  * packed key per query, (order-preserving bits of the score << 32) | ~global_index; after the ranks' key arrays

@@ -54,6 +54,7 @@ class FaceAnalysis:
         self.max_faces = int(max_faces)
         self.gate_config = gate_config or GateConfig()       # the reference's config.json thresholds (GateConfig.from_reference_json)
         self.last_verdict = None                              # of the last best_face(): one of VERDICTS
+        self.last_batch_best = []                             # of the last get_batch(): per image (best face index, FID_GATE_* verdict)
 
     def prepare(self, ctx_id: int = 0, det_size=(640, 640), det_thresh: Optional[float] = None):
         """insightface API compatibility (smart_face_recognition.py:358)"""
@@ -106,6 +107,7 @@ class FaceAnalysis:
         ctx, lib = self.ctx, self.ctx.lib
         net = self.rec.session.compiled()
         out: List[List[Face]] = []
+        bests: List[tuple] = []                               # per image (best face index or -1, FID_GATE_* verdict): process_visits reads it
         step = self.det._max_batch
         for b0 in range(0, len(images), step):
             chunk = images[b0:b0 + step]
@@ -117,6 +119,7 @@ class FaceAnalysis:
             total = sum(len(d) for d, _ in dets)
             if total == 0:
                 out += [[] for _ in range(B)]
+                bests += [(-1, 1)] * B
                 continue
             fr = None if mixed else ctx.to_device(chunk)
             offsets, src = ctx.empty((B + 1,), np.int32), ctx.empty((total,), np.int32)
@@ -140,14 +143,33 @@ class FaceAnalysis:
                 emb[r0:r0 + n] = net.read(net.low.outputs[0], n).reshape(n, 512)
                 normed[r0:r0 + n] = q.download()[:n].astype(np.float32)
             F = max(len(d) for d, _ in dets)
-            quality, side_score, side_flag, _ = face_gates(ctx, post.det, post.kps, post.counts, B, post.cap, F, self.gate_config)
+            quality, side_score, side_flag, best = face_gates(ctx, post.det, post.kps, post.counts, B, post.cap, F, self.gate_config)
+            bests += [(int(i), int(v)) for i, v in best]
             off = offsets.download()
             for b, (det, kpss) in enumerate(dets):
                 r = int(off[b])
                 out.append([Face(bbox=det[i, :4].copy(), det_score=float(det[i, 4]), kps=kpss[i].copy(), embedding=emb[r + i].copy(),
                                  normed_embedding=normed[r + i].copy(), quality={k: float(quality[b, i, j]) for j, k in enumerate(QUALITY_KEYS)},
                                  is_side_face=bool(side_flag[b, i]), side_face_score=int(side_score[b, i])) for i in range(len(det))])
+        self.last_batch_best = bests
         return out
+
+    def process_visits(self, images, store, **thresholds):
+        """The reference's process_visit_data (smart_face_recognition.py:1721-2005) for a list of images (sizes may differ), one visit each, in
+        order: best face and its gates per image (the batch form of best_face, :1473-1519, through get_batch), then `store.group_visits` on the
+        accepted embeddings -- a rejected image is a "no face" visit (:1796-1801).  thresholds: group_visits' duplicate_threshold /
+        grouping_threshold / similarity_threshold (and via).  -> (records, counters): group_visits' record per image plus "gate" (one of
+        VERDICTS), and the reference's counter dict (engine.visit_counters, :1772-1781)."""
+        from .engine import visit_counters
+        faces = self.get_batch(images)
+        emb = np.zeros((len(faces), 512), np.float32)
+        for b, (idx, verdict) in enumerate(self.last_batch_best):
+            if verdict == 0 and 0 <= idx < len(faces[b]):
+                emb[b] = faces[b][idx]["embedding"]
+        records = store.group_visits(emb, **thresholds)
+        for r, (_, verdict) in zip(records, self.last_batch_best):
+            r["gate"] = VERDICTS[verdict]
+        return records, visit_counters(records)
 
     def best_face(self, image: np.ndarray) -> Optional[Face]:
         """The reference's enrolment gate (smart_face_recognition.py:1473-1519): the first highest-det_score face, rejected (None, with

@@ -156,6 +156,8 @@ int lat_fpn_launch(fid_ctx *ctx, const void *in, int B, int H, int W, int Cin_p,
 // match_gemm.hip: the gallery scan on 256 x 256 tiles (query batches > 128 rows against galleries of >= one tile per CU)
 bool match_scan256_applicable(int n, int Gp, int dim, int num_cus);
 int match_scan256_launch(fid_ctx *ctx, const void *q, const void *g, int n, int Gp, int dim, int col0, unsigned long long *amax);
+// match.hip: fid_match's arg-max scan into caller-zeroed packed keys (sortable(score) << 32 | ~row), the context's mutex held by the caller
+int gallery_argmax_keys(fid_ctx *ctx, fid_gallery *g, const void *q, int n, unsigned long long *keys);
 
 // stem_fused.hip: u8 frame -> conv/s2 -> conv -> conv -> maxpool/s2 in one kernel
 int stem_fused_launch(fid_ctx *ctx, const uint8_t *img, int B, int H, int W, const void *w0, const float *b0, const void *w1,

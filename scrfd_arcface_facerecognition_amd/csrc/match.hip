@@ -163,6 +163,11 @@ int gemm_vs_gallery(fid_ctx *ctx, fid_gallery *g, const void *q, int n, int flag
 }
 
 }  // namespace
+
+// the arg-max scan of fid_match for other translation units (visit_group.hip): keys[i] (zeroed by the caller) receives query i's packed key
+int gallery_argmax_keys(fid_ctx *ctx, fid_gallery *g, const void *q, int n, unsigned long long *keys) {
+    return gemm_vs_gallery(ctx, g, q, n, CF_ARGMAX, nullptr, keys);
+}
 }  // namespace fid
 
 extern "C" {

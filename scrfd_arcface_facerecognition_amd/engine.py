@@ -424,6 +424,158 @@ class VectorGallery:
         return merges
 
 
+    # ---- the visit loop (fid_gallery_group): a batch of visits grouped into persons in visit order, one call, one download ------------------------
+    def _next_ids(self):
+        """fresh integer ids above the largest integer id in the store"""
+        k = max((i for i in self.row_of if isinstance(i, (int, np.integer)) and not isinstance(i, bool)), default=-1) + 1
+        while True:
+            yield int(k)
+            k += 1
+
+    def _group_call(self, q_ptr: int, n: int, new_rows, dup: float, group: float, search: float):
+        """fid_gallery_group on n unit fp16 rows at device address q_ptr -> (verdict [n], row [n], score [n], summary [2]) on the host"""
+        ctx = self.ctx
+        rows = np.ascontiguousarray(new_rows, dtype=np.int32)
+        rows_dev = ctx.to_device(rows if len(rows) else np.zeros(1, np.int32))
+        verdict, row, score = ctx.empty((n,), np.int32), ctx.empty((n,), np.int32), ctx.empty((n,), np.float32)
+        summary = ctx.empty((2,), np.int32)
+        check(ctx.lib.fid_gallery_group(ctx.handle, self._gal.handle, C.c_void_p(q_ptr), int(n), C.c_float(dup), C.c_float(group), C.c_float(search),
+                                        C.c_void_p(rows_dev.ptr), len(rows), C.c_void_p(verdict.ptr), C.c_void_p(row.ptr), C.c_void_p(score.ptr),
+                                        C.c_void_p(summary.ptr)))
+        return verdict.download(), row.download(), score.download(), summary.download()
+
+    def group_device(self, q_f16_dev, n: int, ids=None, duplicate_threshold: float = 0.95, grouping_threshold: float = 0.45,
+                     similarity_threshold: float = 0.4):
+        """group_visits for n unit fp16 rows that are already on the device (a pipeline's `q`, the packed rows of get_batch): no upload, no
+        normalisation.  The store grows until n rows are free, the next free rows (in `_free.pop()` order) are handed to fid_gallery_group as
+        new_rows, and after ONE download of verdict / row / score / summary per call the consumed rows are bound to their ids and the unused ones
+        go back to the free list in their old order.  Calls are chunked at the entry point's limit; a DEFERRED suffix is run again."""
+        n = int(n)
+        base = int(_lib._ptr(q_f16_dev).value or 0)
+        if ids is not None and len(ids) != n:
+            raise ValueError(f"group: {len(ids)} ids for {n} visits")
+        if ids is not None:                                         # before anything is written: a clash found later would leave rows bound to no id
+            if len(set(ids)) != n:
+                raise ValueError("group: the ids are not distinct")
+            taken = [i for i in ids if i in self.row_of]
+            if taken:
+                raise ValueError(f"group: id {taken[0]!r} is already stored")
+        fresh = self._next_ids()
+        first_of_empty_store = len(self) == 0
+        records, pos = [], 0
+        while pos < n:
+            m = min(n - pos, GROUP_MAX_VISITS)
+            while len(self._free) < m:
+                self._grow()
+            rows = [self._free.pop() for _ in range(m)]
+            verdict, row, score, summary = self._group_call(base + pos * self.dim * 2, m, rows, duplicate_threshold, grouping_threshold,
+                                                            similarity_threshold)
+            used, decided = int(summary[0]), int(summary[1])
+            self._free.extend(reversed(rows[used:]))
+            if decided == 0:
+                raise RuntimeError("group: the first visit of a call was deferred although a free row was offered")
+            for i in range(decided):
+                v = int(verdict[i])
+                if v == 0:
+                    pid = ids[pos + i] if ids is not None else next(fresh)
+                    self.row_of[pid], self.id_of[int(row[i])] = int(row[i]), pid
+                    sim = float(score[i])
+                    if first_of_empty_store:
+                        sim = 1.0                                   # reference smart_face_recognition.py:1825,1839
+                    first_of_empty_store = False
+                else:
+                    pid, sim = (self.id_of[int(row[i])] if row[i] >= 0 else None), float(score[i])
+                records.append({"verdict": VISIT_VERDICTS[v], "person_id": pid, "similarity": sim})
+            pos += decided
+        return records
+
+    def group_visits(self, embeddings, ids=None, duplicate_threshold: float = 0.95, grouping_threshold: float = 0.45,
+                     similarity_threshold: float = 0.4, via: str = "device"):
+        """The reference's process_visit_data loop (smart_face_recognition.py:1769-1951) for a batch of embeddings in visit order: per visit
+        is_duplicate_image (:2618-2652, `duplicate_similarity_threshold`), search_person (:1619-1643, `similarity_threshold`), grouping with
+        the best hit at `grouping_threshold_file` (:1859-1861; default 0.45 = reference config.json:22) or add_person (:1531-1602).  A visit
+        that becomes a new person is a candidate for every later visit of the call; a recognised one is not stored.
+        -> one record per visit: {"verdict": one of VISIT_VERDICTS, "person_id": the id grouped with / duplicate of / newly assigned (None: no
+        face), "similarity"}.  ids[i] = the id visit i gets if it is new (default: fresh integers above the largest integer id stored).  An
+        all-zero (or non-finite) embedding is a "no face" visit.  If the store was empty, the first new person reports similarity 1.0 (:1825).
+        via="device": fid_gallery_group, one call per 65 536 visits.  via="loop": the same answer by the reference's own sequence, one visit at a
+        time on what existed before (fid_gallery_topk with k = 1 and k = 5, then upsert) -- the baseline of tools/bench_group.py.  The one
+        difference: upsert re-normalises the fp32 embedding, the device path copies the query's fp16 row, so stored bits may differ in the
+        last place."""
+        emb = np.ascontiguousarray(embeddings, dtype=np.float32).reshape(-1, self.dim)
+        n = emb.shape[0]
+        if n == 0:
+            return []
+        e = self.ctx.to_device(emb)
+        q = self.ctx.empty((n, self.dim), np.float16)
+        check(self.ctx.lib.fid_l2_normalize_f16(self.ctx.handle, C.c_void_p(e.ptr), n, self.dim, C.c_void_p(q.ptr)))
+        if via == "device":
+            return self.group_device(q, n, ids, duplicate_threshold, grouping_threshold, similarity_threshold)
+        if via != "loop":
+            raise ValueError(f"group_visits: via={via!r}, expected 'device' or 'loop'")
+        if ids is not None and (len(ids) != n or len(set(ids)) != n or any(i in self.row_of for i in ids)):
+            raise ValueError(f"group: {n} distinct ids that are not stored yet are needed")
+        ctx, lib = self.ctx, self.ctx.lib
+        has_face = (q.download().view(np.uint16) & 0x7FFF).any(axis=1)
+        fresh = self._next_ids()
+        i1, s1, i5, s5 = ctx.empty((1, 1), np.int32), ctx.empty((1, 1), np.float32), ctx.empty((1, 5), np.int32), ctx.empty((1, 5), np.float32)
+        records = []
+        for i in range(n):
+            if not has_face[i]:
+                records.append({"verdict": VISIT_VERDICTS[3], "person_id": None, "similarity": 0.0})
+                continue
+            if len(self) == 0:                                      # :1820-1851: the first person of an empty store, similarity 1.0
+                pid = ids[i] if ids is not None else next(fresh)
+                self.upsert([pid], emb[i:i + 1])
+                records.append({"verdict": VISIT_VERDICTS[0], "person_id": pid, "similarity": 1.0})
+                continue
+            qi = C.c_void_p(q.ptr + i * self.dim * 2)
+            # (the searches run with threshold 0 and `>=` is applied here: Qdrant's score_threshold keeps scores >= it, fid_gallery_topk's is strict)
+            check(lib.fid_gallery_topk(ctx.handle, self._gal.handle, qi, 1, 1, C.c_float(0.0), C.c_void_p(i1.ptr), C.c_void_p(s1.ptr)))
+            j, s = int(i1.download()[0, 0]), float(s1.download()[0, 0])
+            if j >= 0 and s >= np.float32(duplicate_threshold):
+                records.append({"verdict": VISIT_VERDICTS[2], "person_id": self.id_of[j], "similarity": s})
+                continue
+            check(lib.fid_gallery_topk(ctx.handle, self._gal.handle, qi, 1, 5, C.c_float(0.0), C.c_void_p(i5.ptr), C.c_void_p(s5.ptr)))
+            I, S = i5.download()[0], s5.download()[0]
+            hits = [(int(a), float(b)) for a, b in zip(I, S) if a >= 0 and b >= np.float32(similarity_threshold)]
+            sim = hits[0][1] if hits else 0.0
+            if hits and sim >= np.float32(grouping_threshold):
+                records.append({"verdict": VISIT_VERDICTS[1], "person_id": self.id_of[hits[0][0]], "similarity": sim})
+                continue
+            pid = ids[i] if ids is not None else next(fresh)
+            self.upsert([pid], emb[i:i + 1])
+            records.append({"verdict": VISIT_VERDICTS[0], "person_id": pid, "similarity": sim})
+        return records
+
+
+VISIT_VERDICTS = ("new", "recognised", "duplicate", "no face", "deferred")        # FID_VISIT_* (include/faceid.h)
+GROUP_MAX_VISITS = 65536                                                          # FID_GROUP_MAX_VISITS
+
+
+def visit_counters(records):
+    """the reference's per-run counter dict (smart_face_recognition.py:1772-1781, summed over the visits :1967-1975) from group_visits' records:
+    `processed` counts the visits that passed the duplicate check (:1817), i.e. recognised + new; the keys only the download / SQL layer can
+    raise stay 0"""
+    out = {"processed": 0, "recognized": 0, "new_persons": 0, "no_faces": 0, "low_quality": 0, "download_failed": 0, "duplicate_faces": 0,
+           "low_similarity": 0}
+    for r in records:
+        v = r["verdict"]
+        if v == "no face":
+            out["no_faces"] += 1
+        elif v == "duplicate":
+            out["duplicate_faces"] += 1
+        elif v == "recognised":
+            out["processed"] += 1
+            out["recognized"] += 1
+        elif v == "new":
+            out["processed"] += 1
+            out["new_persons"] += 1
+        else:
+            raise ValueError(f"visit_counters: verdict {v!r}")
+    return out
+
+
 def merge_from_pairs(ids, pairs, threshold: float):
     """The reference's greedy merge loop (smart_face_recognition.py:2755-2792) on a pair list [(id_a, id_b, score)] (each unordered pair at most
     once, either order): ids in ascending order; every id that is still alive absorbs each alive LARGER id it is paired with at score >= threshold,
