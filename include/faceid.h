@@ -250,7 +250,8 @@ int fid_face_gates(fid_ctx *ctx, const float *det_dev, const float *kps_dev, con
                    int faces_per_frame, const double *pose_dev, const fid_gate_config *cfg, float *quality_dev,
                    int32_t *side_dev, int32_t *best_dev);
 
-/* ---- embeddings -> unit fp16 rows: the norm half of reference utils/helpers.py:120-123 ------ */
+/* ---- embeddings -> unit fp16 rows: the norm half of reference utils/helpers.py:120-123 ------
+ * A row whose fp32 sum of squares is not in (0, inf) -- all zero, a NaN or inf element, squares that overflow or underflow -- becomes an all +0.0 row. */
 int fid_l2_normalize_f16(fid_ctx *ctx, const float *emb_dev, int n, int dim, void *out_f16_dev);
 /* the same for the n = B * faces_per_frame face slots of a batch: slot (b, f) with f >= counts[b] holds no face (reference
  * main.py:132 iterates detected faces only) and is written as a zero row, which scores 0 against every gallery row and so never
