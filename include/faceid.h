@@ -285,6 +285,28 @@ int fid_gallery_data(fid_gallery *g, void **unit_rows_dev);
 int fid_gallery_topk(fid_ctx *ctx, fid_gallery *g, const void *query_f16_dev, int n, int k, float thresh,
                      int32_t *idx_dev, float *score_dev);
 int fid_gallery_set_rows(fid_ctx *ctx, fid_gallery *g, const int32_t *rows_host, const float *emb_host, int n);
+/* Fused top-k search: the contract of fid_gallery_topk for ANY 1 <= k <= FID_TOPK_MAX (`limit` of qdrant_manager.py:138-183 is an arbitrary
+ * integer), computed without the n x G score matrix: per query the k best (score, row) pairs, score descending, row ascending among equal
+ * scores; only scores strictly > max(0, thresh) count and a query with fewer hits is padded with (-1, 0.0) -- all n x k entries of idx_dev
+ * int32 [n, k] and score_dev float [n, k] are always written.  A NaN score, a zero (deleted / free) row and a padding row >= G are never reported.
+ * It IS fid_topk_keys(first_row = 0) followed by fid_topk_merge(parts = 1), the keys kept in the scratch arena.
+ * FID_E_INVALID, nothing enqueued, outputs untouched: a NULL pointer, n <= 0, k < 1 or k > FID_TOPK_MAX, a NaN thresh, dim % 32 != 0.
+ * Asynchronous on the context's stream; no host synchronisation beyond the scratch-arena rule of fid_match (see fid_gallery_group).
+ * FID_TOPK_SLICES=<S> (read per call) forces the number of gallery slices the scan is cut into; the answer does not depend on it. */
+#define FID_TOPK_MAX 32
+int fid_gallery_search(fid_ctx *ctx, fid_gallery *g, const void *query_f16_dev, int n, int k, float thresh,
+                       int32_t *idx_dev, float *score_dev);
+/* Top-k over a gallery sharded by contiguous row blocks (the top-k twin of fid_match_keys / fid_match_merge below).  fid_topk_keys scans THIS
+ * shard's rows (global index of its row 0 = first_row; first_row >= 0 and first_row + G_padded < 2^31) and writes keys_dev uint64 [n, k]: per
+ * query its k best candidates as fid_match_keys' key, (order-preserving bits of the score << 32) | ~(first_row + row), descending, 0 = no
+ * candidate.  Only scores > 0 that are not NaN become keys; no threshold yet.  After the shards' arrays have been all-gathered into
+ * [parts, n, k], fid_topk_merge takes the k largest of a query's parts x k keys -- ignoring 0 and keys whose index is >= G_total -- and
+ * applies the strict threshold: with contiguous shards exactly the answer of one fid_gallery_search over the whole gallery.
+ * FID_E_INVALID as for fid_gallery_search, and parts <= 0, G_total <= 0, a first_row outside the range above. */
+int fid_topk_keys(fid_ctx *ctx, fid_gallery *g, const void *query_f16_dev, int n, int k, int first_row,
+                  uint64_t *keys_dev);
+int fid_topk_merge(fid_ctx *ctx, const uint64_t *keys_dev, int parts, int n, int k, int G_total, float thresh,
+                   int32_t *idx_dev, float *score_dev);
 /* Range search / similarity join: every (query, gallery row) with cosine >= thresh (and > 0), not the best k -- what the product layer's
  * duplicate merge asks of its vector store (reference smart_face_recognition.py:2761-2766: `search_similar(k=len(persons), threshold)`;
  * qdrant_manager.py:137-183, whose score_threshold keeps scores >= the threshold).  A zero (deleted / free) row and a NaN never hit.

@@ -309,16 +309,28 @@ class VectorGallery:
         check(self.ctx.lib.fid_gallery_set_rows(self.ctx.handle, self._gal.handle, rows.ctypes.data_as(_lib.c_i32_p),
                                                 zeros.ctypes.data_as(C.c_void_p), len(rows)))
 
-    def search(self, embeddings, k: int = 5, score_threshold: float = 0.0):
-        """-> per query a list of (id, score), best first (at most k, only scores > max(0, threshold))."""
+    TOPK_MAX = 32                   # FID_TOPK_MAX of include/faceid.h
+    MATRIX_KS = (1, 2, 4, 5, 8)     # the k fid_gallery_topk serves
+
+    def search(self, embeddings, k: int = 5, score_threshold: float = 0.0, via: Optional[str] = None):
+        """-> per query a list of (id, score), best first (at most k, only scores > max(0, threshold)).
+        via=None: fid_gallery_topk (the score matrix in scratch) for the k it serves, the fused fid_gallery_search for every other k up to 32;
+        via="fused" / "matrix" force one of them (equal answers; which is the faster default is tools/bench_topk.py's question)."""
+        k = int(k)
+        if via not in (None, "fused", "matrix"):
+            raise ValueError("via must be None, 'fused' or 'matrix', not %r" % (via,))
+        if k < 1 or k > self.TOPK_MAX:
+            raise ValueError("k = %d is outside 1 .. %d: range_search returns every hit at or above a threshold" % (k, self.TOPK_MAX))
+        if via == "matrix" and k not in self.MATRIX_KS:
+            raise ValueError("via='matrix' serves k in %s only, not %d" % (self.MATRIX_KS, k))
+        fn = self.ctx.lib.fid_gallery_topk if via == "matrix" or (via is None and k in self.MATRIX_KS) else self.ctx.lib.fid_gallery_search
         emb = np.ascontiguousarray(embeddings, dtype=np.float32).reshape(-1, self.dim)
         n = emb.shape[0]
         e = self.ctx.to_device(emb)
         q = self.ctx.empty((n, self.dim), np.float16)
         check(self.ctx.lib.fid_l2_normalize_f16(self.ctx.handle, C.c_void_p(e.ptr), n, self.dim, C.c_void_p(q.ptr)))
         idx, sc = self.ctx.empty((n, k), np.int32), self.ctx.empty((n, k), np.float32)
-        check(self.ctx.lib.fid_gallery_topk(self.ctx.handle, self._gal.handle, C.c_void_p(q.ptr), n, int(k), float(score_threshold),
-                                            C.c_void_p(idx.ptr), C.c_void_p(sc.ptr)))
+        check(fn(self.ctx.handle, self._gal.handle, C.c_void_p(q.ptr), n, k, float(score_threshold), C.c_void_p(idx.ptr), C.c_void_p(sc.ptr)))
         I, S = idx.download(), sc.download()
         return [[(self.id_of[int(j)], float(s)) for j, s in zip(I[r], S[r]) if j >= 0] for r in range(n)]
 

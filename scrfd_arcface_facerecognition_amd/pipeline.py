@@ -94,6 +94,15 @@ class FacePipeline:
         check(self.ctx.lib.fid_match_merge(self.ctx.handle, _lib._ptr(keys_all), int(parts), int(n), int(gallery_total),
                                            float(thresh), _lib._ptr(idx), _lib._ptr(score)))
 
+    def topk_keys(self, gallery: Gallery, q, n, k, first_row, keys):
+        """this rank's shard of a row-sharded gallery: the k best packed keys per query, keys [n, k] uint64, descending, 0 = no candidate"""
+        check(self.ctx.lib.fid_topk_keys(self.ctx.handle, gallery.handle, _lib._ptr(q), int(n), int(k), int(first_row), _lib._ptr(keys)))
+
+    def topk_merge(self, keys_all, parts, n, k, gallery_total, thresh, idx, score):
+        """keys_all [parts, n, k] (the all-gathered shards) -> idx / score [n, k]: the answer of one top-k search over the whole gallery"""
+        check(self.ctx.lib.fid_topk_merge(self.ctx.handle, _lib._ptr(keys_all), int(parts), int(n), int(k), int(gallery_total),
+                                          float(thresh), _lib._ptr(idx), _lib._ptr(score)))
+
     def run_step(self, frames_dev, H, W, gallery: Gallery, thresh: float = 0.4):
         """One full pass over one batch; asynchronous (results stay on the device)."""
         if self.det.ctx is not self.ctx:
