@@ -360,6 +360,37 @@ int fid_match_keys(fid_ctx *ctx, fid_gallery *g, const void *query_f16_dev, int 
 int fid_match_merge(fid_ctx *ctx, const uint64_t *keys_dev, int parts, int n, int G_total, float thresh,
                     int32_t *idx_dev, float *score_dev);
 
+/* ---- 1:1 verification: P pairs of embeddings -> P (score, verdict) records and the counters of the batch loop.  Replaces the reference's
+ * compare_face_images (smart_face_recognition.py:878-963), calculate_face_similarity (:965-982) and the tallies of process_face_comparisons
+ * (:1088-1094, :1108-1110); compare_face_from_api.py is the same workflow as a script.
+ * emb_dev [n_rows, dim]: RAW fp32 embeddings, e.g. the recogniser's output tensor (fid_net_tensor) as it is -- not normalised, not fp16.
+ * pairs_dev int32 [P, 2] names the two sides of each pair:
+ *   offsets_dev == NULL: entries are rows of emb_dev; -1 = the image is missing (FID_PAIR_NO_IMAGE); -2 or any other value outside
+ *                        [0, n_rows) = no face (FID_PAIR_NO_FACE).
+ *   offsets_dev int32 [n_img + 1] (what fid_face_pack writes with max_per_frame = 1): entries are image indices; -1 or any value outside
+ *                        [0, n_img) = FID_PAIR_NO_IMAGE; image i is row offsets[i] when offsets[i+1] > offsets[i] and 0 <= offsets[i] < n_rows,
+ *                        otherwise FID_PAIR_NO_FACE.
+ *   NO_IMAGE on either side wins over NO_FACE (the reference checks the downloads first, :896, then the faces, :915).  A row that is not
+ *   valid is never read.
+ * labels_dev (optional, may be NULL) int32 [P]: 1 / 0 = the API's `approve` of the pair, any other value (-1) = none.
+ * Outputs (device): score float [P], verdict int32 [P] (FID_PAIR_*).  A valid pair: three fp32 sums a.b, a.a, b.b reduced in a fixed order
+ * (bitwise reproducible), score = dot / (sqrtf(aa) * sqrtf(bb)) in the reference's order (:978) with correctly rounded divide and square root;
+ * FID_PAIR_SAME iff score > thresh, strictly (:932).  A zero row gives a NaN score and FID_PAIR_DIFFERENT, as `nan > t` does in the reference.
+ * An error pair: score = 0.0f (the reference's 'confidence': 0.0).
+ * counters_dev int32 [8] is ADDED TO, never cleared (zero it once with fid_memset; chunks then sum up): 0 processed, 1 same, 2 different,
+ * 3 no-image errors, 4 no-face errors, 5 labelled pairs, 6 labelled pairs whose label == (verdict == FID_PAIR_SAME) -- an error pair counts as
+ * "not same" (:1082) --, 7 untouched.
+ * FID_E_INVALID, nothing enqueued, outputs untouched: P < 0, n_rows < 0, n_img < 0, dim <= 0 or dim % 4 != 0, emb_dev not 16-byte aligned,
+ * emb_dev == NULL with n_rows > 0, a NULL pair table or output pointer with P > 0.  P == 0 returns FID_OK without a launch.
+ * One launch, asynchronous on the context's stream, no scratch arena. */
+#define FID_PAIR_DIFFERENT 0
+#define FID_PAIR_SAME      1
+#define FID_PAIR_NO_IMAGE  2   /* 'Could not download one or both images' (:896-903) */
+#define FID_PAIR_NO_FACE   3   /* 'Could not detect faces in one or both images' (:915-922) */
+int fid_pair_verify(fid_ctx *ctx, const float *emb_dev, int n_rows, int dim, const int32_t *pairs_dev, int P,
+                    const int32_t *offsets_dev, int n_img, const int32_t *labels_dev, float thresh, float *score_dev,
+                    int32_t *verdict_dev, int32_t *counters_dev);
+
 /* ---- the path's one collective (no reference analogue: the reference is single-process; spec = BASELINE.json
  * north_star "a single RCCL all-gather over xGMI of per-rank embeddings before the gallery match").
  * One process per GPU.  Rank 0 calls fid_comm_unique_id and the host hands the FID_COMM_ID_BYTES bytes to every

@@ -36,6 +36,14 @@ def face_gates(ctx, det_dev, kps_dev, counts_dev, batch: int, cap: int, faces_pe
     return quality.download(), sd & 0xFFFF, (sd >> 16).astype(bool), best.download()
 
 
+def _approve_label(approve) -> int:
+    """a comparison record's `approve` as fid_pair_verify's label: 1 / 0 where `approve == True` / `approve == False` holds (bools, and the
+    numbers 1 and 0 an API may send instead: what `record['approve'] == same_person`, smart_face_recognition.py:1082, can ever match), else -1"""
+    if isinstance(approve, (bool, int, float, np.bool_, np.integer, np.floating)):
+        return 1 if approve == 1 else 0 if approve == 0 else -1
+    return -1
+
+
 class Face(dict):
     """dict with attribute access, like insightface's Face"""
     __getattr__ = dict.get
@@ -170,6 +178,133 @@ class FaceAnalysis:
         for r, (_, verdict) in zip(records, self.last_batch_best):
             r["gate"] = VERDICTS[verdict]
         return records, visit_counters(records)
+
+    def compare_pairs(self, images_a, images_b, threshold: float = 0.4, labels=None, return_embeddings: bool = False):
+        """The reference's compare_face_images (smart_face_recognition.py:878-963) for P image pairs: pair p = (images_a[p], images_b[p]); an
+        image may be None (its download failed, :896) and the images may differ in size.  Per chunk of `min(det max_batch, max_faces) // 2`
+        pairs -- a chunk holds whole pairs -- the present images run as ONE batch: detect (max_num = 0; the mixed-size path when shapes differ,
+        as get_batch chooses), fid_face_pack with max_per_frame = 1 (the first NMS survivor = `faces[0]`, :925-926: only that face is
+        aligned and embedded), packed warp, recogniser, then fid_pair_verify on the recogniser's output tensor in place: fp32 cosine (:978),
+        strict `> threshold` (:932), error verdicts and counters.  No embedding is downloaded unless `return_embeddings` is set; the chunk's
+        detections still are (the detector's own fetch, which also reports a capacity overflow): they tell the host how many rows to embed.
+        labels: optional [P] of True / False / None (or 1 / 0 / -1), the API's `approve`.
+        -> (results, counters): per pair {"same_person", "confidence", "threshold_used", "error"} (:936-943; "error" is one of the reference's
+        two messages or None) -- with return_embeddings also "embedding1" / "embedding2" (float32 [D] or None) and "bbox1" / "bbox2" (the chosen
+        face's det row [5] or None) --, and engine.pair_counters' dict."""
+        from .engine import PAIR_ERRORS, pair_counters
+        from .pipeline import pair_image_table
+        sides = (list(images_a), list(images_b))
+        P = len(sides[0])
+        if len(sides[1]) != P:
+            raise ValueError(f"compare_pairs: {P} first images, {len(sides[1])} second images")
+        step = min(self.det._max_batch, self.max_faces) // 2
+        if step < 1:
+            raise ValueError("compare_pairs: the detector's max_batch and max_faces must both be >= 2 (a chunk holds whole pairs)")
+        if P == 0:
+            return [], pair_counters(np.zeros(8, np.int32))
+        sides = tuple([None if im is None else np.ascontiguousarray(im, dtype=np.uint8) for im in s] for s in sides)
+        present = tuple([im is not None for im in s] for s in sides)
+        ctx, lib = self.ctx, self.ctx.lib
+        net = self.rec.session.compiled()
+        chunks = [pair_image_table(present[0], present[1], p0, min(p0 + step, P)) for p0 in range(0, P, step)]
+        pairs = ctx.to_device(np.concatenate([t for _, t in chunks]))
+        lab = None
+        if labels is not None:
+            lab = np.array([-1 if v is None else int(v) for v in labels], np.int32)
+            if lab.shape[0] != P:
+                raise ValueError(f"compare_pairs: {lab.shape[0]} labels for {P} pairs")
+            lab = ctx.to_device(lab)
+        out = ctx.empty((2 * P + 8,), np.int32).zero()        # score [P] | verdict [P] | counters [8]: one download at the end
+        offsets, src = ctx.empty((2 * step + 1,), np.int32).zero(), ctx.empty((2 * step,), np.int32)
+        crops = ctx.empty((2 * step, 112, 112, 3), np.uint8)
+        emb = [[None] * P, [None] * P]
+        bbox = [[None] * P, [None] * P]
+        for ci, (run, _) in enumerate(chunks):
+            p0 = ci * step
+            Pc = min(step, P - p0)
+            imgs = [sides[side][p] for p, side in run]
+            n, total, emb_ptr, dim, dets = len(imgs), 0, None, 512, []
+            if n:
+                mixed = len({im.shape for im in imgs}) > 1
+                if mixed:
+                    batch = ctx.image_batch(imgs)
+                    dets = self.det._detect_chunk_ragged(imgs, 0, "max", batch)
+                else:
+                    chunk = np.stack(imgs)
+                    fr = ctx.to_device(chunk)                 # one upload: the detector and the warp read the same frames
+                    dets = self.det._detect_chunk(chunk, 0, "max", fr)
+                post = self.det._postprocessor()
+                total = sum(1 for d, _ in dets if len(d))
+                check(lib.fid_face_pack(ctx.handle, C.c_void_p(post.counts.ptr), n, post.cap, 1, C.c_void_p(offsets.ptr), C.c_void_p(src.ptr), n))
+            if total:
+                if mixed:
+                    check(lib.fid_align_crops_packed_ragged(ctx.handle, *batch.args(), n, C.c_void_p(post.kps.ptr), post.cap, C.c_void_p(src.ptr),
+                                                            total, C.c_void_p(crops.ptr), None))
+                else:
+                    check(lib.fid_align_crops_packed(ctx.handle, C.c_void_p(fr.ptr), n, chunk.shape[1], chunk.shape[2], C.c_void_p(post.kps.ptr),
+                                                     post.cap, C.c_void_p(src.ptr), total, C.c_void_p(crops.ptr), None))
+                net.run_device(crops, total)
+                emb_ptr, (eh, ew, ec, ecp), dt = net.tensor(net.low.outputs[0])
+                if dt != np.float32 or (eh, ew) != (1, 1) or ec != ecp:
+                    raise RuntimeError(f"compare_pairs: the recogniser's output {(eh, ew, ec, ecp)} {dt} is not a dense fp32 row per face")
+                dim = ecp
+            # (a chunk without any face, or without any image, still goes through the entry point: its errors are counted there)
+            check(lib.fid_pair_verify(ctx.handle, C.c_void_p(emb_ptr) if total else None, total, dim, C.c_void_p(pairs.ptr + 8 * p0), Pc,
+                                      C.c_void_p(offsets.ptr), n, C.c_void_p(lab.ptr + 4 * p0) if lab is not None else None,
+                                      C.c_float(threshold), C.c_void_p(out.ptr + 4 * p0), C.c_void_p(out.ptr + 4 * (P + p0)),
+                                      C.c_void_p(out.ptr + 8 * P)))
+            if return_embeddings and total:
+                e = net.read(net.low.outputs[0], total).reshape(total, -1)
+                off = offsets.download()
+                for i, (p, side) in enumerate(run):
+                    if len(dets[i][0]):
+                        emb[side][p], bbox[side][p] = e[off[i]].copy(), dets[i][0][0].copy()
+        got = out.download()
+        score, verdict = got[:P].view(np.float32), got[P:2 * P]
+        results = []
+        for p in range(P):
+            r = {"same_person": bool(verdict[p] == 1), "confidence": float(score[p]), "threshold_used": threshold, "error": PAIR_ERRORS[verdict[p]]}
+            if return_embeddings:
+                r.update(embedding1=emb[0][p], embedding2=emb[1][p], bbox1=bbox[0][p], bbox2=bbox[1][p])
+            results.append(r)
+        return results, pair_counters(got[2 * P:])
+
+    def process_face_comparisons(self, records, loader=None, max_comparisons: Optional[int] = None, threshold: float = 0.4):
+        """The reference's process_face_comparisons (smart_face_recognition.py:1023-1143) on compare_pairs: records are its comparison records
+        (`image1_url`, `image2_url`, `approve` and the metadata keys of :1067-1084; a missing metadata key reads None); loader(url) returns a uint8
+        BGR image or None (default: pipeline._read_image on file paths -- fetching from the network is the caller's business).
+        -> the summary dict of :1112-1122 (the empty form :1036-1043 for no records); per-record fields as :1067-1084.  The summary's
+        `api_matches` / `total_with_api_data` are counted on the host exactly as :1108-1110 do (every record counts, `None == False` is no match);
+        the device's labelled / label_matches counters take `approve` equal to True / 1 or False / 0 as a label and anything else as none."""
+        from .pipeline import _read_image
+        if not records:
+            return {"total_comparisons": 0, "processed": 0, "same_person": 0, "different_person": 0, "errors": 0, "results": []}
+        records = list(records)
+        if max_comparisons and len(records) > max_comparisons:
+            records = records[:max_comparisons]
+        loader = loader or _read_image
+
+        def load(url):
+            im = loader(url) if url is not None else None
+            return im if isinstance(im, np.ndarray) and im.ndim == 3 and im.shape[2] == 3 and im.size else None
+
+        approve = [r.get("approve") for r in records]
+        res, counters = self.compare_pairs([load(r.get("image1_url")) for r in records], [load(r.get("image2_url")) for r in records], threshold,
+                                           labels=[_approve_label(a) for a in approve])
+        results = []
+        for r, c, v in zip(records, res, approve):
+            out = {k: r.get(k) for k in ("comparison_id", "event_id", "branch_id", "created_at", "customer_info", "matched_info")}
+            out.update(api_approve=v, our_result=c["same_person"], confidence=c["confidence"], threshold_used=c["threshold_used"],
+                       image1_url=r.get("image1_url"), image2_url=r.get("image2_url"), error=c["error"],
+                       match_status="SAME" if c["same_person"] else "DIFFERENT", api_vs_our_match=v == c["same_person"],
+                       raw_data=r.get("raw_data", {}))
+            results.append(out)
+        api_matches = sum(1 for r in results if r.get("api_vs_our_match") is True)                                        # :1108-1110
+        total_with_api_data = sum(1 for r in results if "api_vs_our_match" in r and r["api_vs_our_match"] is not None)
+        return {"total_comparisons": len(records), "processed": len(results), "same_person": counters["same_person"],
+                "different_person": counters["different_person"], "errors": counters["errors"],
+                "accuracy_vs_api": (api_matches / total_with_api_data * 100) if total_with_api_data > 0 else 0, "api_matches": api_matches,
+                "total_with_api_data": total_with_api_data, "results": results}
 
     def best_face(self, image: np.ndarray) -> Optional[Face]:
         """The reference's enrolment gate (smart_face_recognition.py:1473-1519): the first highest-det_score face, rejected (None, with

@@ -588,6 +588,51 @@ def visit_counters(records):
     return out
 
 
+PAIR_VERDICTS = ("different", "same", "no image", "no face")                     # FID_PAIR_* (include/faceid.h)
+PAIR_ERRORS = (None, None, "Could not download one or both images", "Could not detect faces in one or both images")   # :900, :919
+PAIR_COUNTER_KEYS = ("processed", "same_person", "different_person", "no_image", "no_face", "labelled", "label_matches")
+
+
+def pair_counters(counters) -> dict:
+    """fid_pair_verify's counter slots as a dict; `errors` = no_image + no_face is the error_count of smart_face_recognition.py:1089-1090"""
+    out = {k: int(v) for k, v in zip(PAIR_COUNTER_KEYS, counters)}
+    out["errors"] = out["no_image"] + out["no_face"]
+    return out
+
+
+def verify_pairs(ctx: Context, feats1, feats2, threshold: float = 0.4, labels=None):
+    """The reference's calculate_face_similarity and verdict (smart_face_recognition.py:965-982, :928-932) for P pairs at once: feats1, feats2
+    host [P, D] raw fp32 embeddings (D % 4 == 0), pair p = (feats1[p], feats2[p]); labels: optional [P] of 1 / 0 / -1 (the API's approve, -1 = none).
+    One upload (both matrices, the pair table and the labels travel as ONE buffer), one fid_pair_verify, one download.
+    -> (score float32 [P], verdict int32 [P] (FID_PAIR_*), counters int32 [8])."""
+    a, b = np.ascontiguousarray(feats1, dtype=np.float32), np.ascontiguousarray(feats2, dtype=np.float32)
+    if a.ndim != 2 or a.shape != b.shape:
+        raise ValueError(f"verify_pairs: feats1 {a.shape} and feats2 {b.shape} must be two [P, D] matrices of one shape")
+    P, D = a.shape
+    if P == 0:
+        return np.zeros(0, np.float32), np.zeros(0, np.int32), np.zeros(8, np.int32)
+    lab = None
+    if labels is not None:
+        lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        if lab.shape[0] != P:
+            raise ValueError(f"verify_pairs: {lab.shape[0]} labels for {P} pairs")
+    emb_bytes = 2 * P * D * 4                                   # a multiple of 16: D % 4 == 0 is checked by the library
+    host = np.empty(emb_bytes + P * 8 + (P * 4 if lab is not None else 0), np.uint8)
+    host[:emb_bytes // 2] = a.view(np.uint8).reshape(-1)
+    host[emb_bytes // 2:emb_bytes] = b.view(np.uint8).reshape(-1)
+    pairs = np.stack([np.arange(P, dtype=np.int32), np.arange(P, 2 * P, dtype=np.int32)], axis=1)
+    host[emb_bytes:emb_bytes + P * 8] = pairs.view(np.uint8).reshape(-1)
+    if lab is not None:
+        host[emb_bytes + P * 8:] = lab.view(np.uint8)
+    inp = ctx.to_device(host)
+    out = ctx.empty((2 * P + 8,), np.int32).zero()              # score [P] | verdict [P] | counters [8]
+    check(ctx.lib.fid_pair_verify(ctx.handle, C.c_void_p(inp.ptr), 2 * P, D, C.c_void_p(inp.ptr + emb_bytes), P, None, 0,
+                                  C.c_void_p(inp.ptr + emb_bytes + P * 8) if lab is not None else None, C.c_float(threshold),
+                                  C.c_void_p(out.ptr), C.c_void_p(out.ptr + 4 * P), C.c_void_p(out.ptr + 8 * P)))
+    got = out.download()
+    return got[:P].view(np.float32).copy(), got[P:2 * P].copy(), got[2 * P:].copy()
+
+
 def merge_from_pairs(ids, pairs, threshold: float):
     """The reference's greedy merge loop (smart_face_recognition.py:2755-2792) on a pair list [(id_a, id_b, score)] (each unordered pair at most
     once, either order): ids in ascending order; every id that is still alive absorbs each alive LARGER id it is paired with at score >= threshold,

@@ -106,10 +106,11 @@ class SCRFD:
             results += self._detect_chunk(chunk, max_num, metric)
         return results
 
-    def _detect_chunk(self, images, max_num, metric):
+    def _detect_chunk(self, images, max_num, metric, frames=None):
+        """`frames`: the chunk already on the device (a caller that reads the frames again, e.g. for the warp, uploads them once)"""
         B, H, W, _ = images.shape
         in_w, in_h = self.input_size
-        frames = self.ctx.to_device(images)
+        frames = self.ctx.to_device(images) if frames is None else frames
         if (H, W) == (in_h, in_w):
             det_in = frames
         else:                                      # scrfd.py:123-138 on the device

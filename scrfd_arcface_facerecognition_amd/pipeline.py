@@ -244,6 +244,21 @@ def packed_layout(counts, cap: int, max_per_frame: int, row_cap: int) -> Tuple[n
     return offsets.astype(np.int32), src
 
 
+def pair_image_table(present_a, present_b, p0: int, p1: int) -> Tuple[List[Tuple[int, int]], np.ndarray]:
+    """The images one chunk of a pair list runs, stated on the host (FaceAnalysis.compare_pairs): pairs p0 .. p1 - 1, present_a[p] / present_b[p]
+    = "image a / b of pair p exists" (the reference's download succeeded, smart_face_recognition.py:893-896).
+    -> run: [(p, side)] (side 0 = a, 1 = b) in the order a_p0, b_p0, a_p0+1 ... with absent images skipped: image i of the chunk's batch;
+       table int32 [p1 - p0, 2]: the batch index of each side, -1 for an absent image -- fid_pair_verify's pair table in its image-index form."""
+    run: List[Tuple[int, int]] = []
+    table = np.full((max(p1 - p0, 0), 2), -1, np.int32)
+    for p in range(p0, p1):
+        for side, present in enumerate((present_a, present_b)):
+            if present[p]:
+                table[p - p0, side] = len(run)
+                run.append((p, side))
+    return run, table
+
+
 class PackedFacePipeline(FacePipeline):
     """FacePipeline on a dense (packed) face list: EVERY face the detector returns for the batch -- `max_num = 0`, the reference's
     default (main.py:130-134 with models/scrfd.py:159-177), or its top-`max_num` per frame -- is one row of a row table

@@ -87,6 +87,14 @@ def compute_similarity(feat1: np.ndarray, feat2: np.ndarray, *, ctx=None) -> np.
     return np.float32(cos[0, 0])
 
 
+def compute_similarities(feats1, feats2, *, ctx=None) -> np.ndarray:
+    """The cosine of reference smart_face_recognition.py:965-982 (the same formula as helpers.py:110-123) for P pairs at once, in fp32 on the
+    raw rows (fid_pair_verify; no fp16 unit rows in between): feats1, feats2 [P, D] -> float32 [P].  A zero row gives NaN, as numpy does."""
+    from ..engine import verify_pairs
+    score, _, _ = verify_pairs(_ctx(ctx), feats1, feats2, threshold=0.0)
+    return score
+
+
 def match_gallery(embeddings, gallery, thresh, *, ctx=None, return_matrix=False):
     """The gallery scan of reference main.py:136-142 for many faces at once.
     embeddings [N,D], gallery [G,D] (raw, un-normalised) -> (idx int32 [N] (-1 = Unknown), score float32 [N])."""
