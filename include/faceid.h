@@ -350,6 +350,26 @@ enum { FID_VISIT_NEW = 0, FID_VISIT_RECOGNISED = 1, FID_VISIT_DUPLICATE = 2, FID
 int fid_gallery_group(fid_ctx *ctx, fid_gallery *g, const void *query_f16_dev, int n, float dup_thresh, float group_thresh,
                       float search_thresh, const int32_t *new_rows_dev, int n_new_rows, int32_t *verdict_dev, int32_t *row_dev,
                       float *score_dev, int32_t *summary_dev);
+/* Merging duplicate persons of the store: the reference's maintenance pass find_and_merge_duplicates (smart_face_recognition.py:2726-2797, loop
+ * :2755-2792, with merge_duplicate_persons :2679-2724; config.json merge_duplicate_threshold = 0.8) as ONE asynchronous call that returns one
+ * keeper per person, not one record per pair.
+ * rows_dev: int32 [n], the gallery rows of the persons IN PROCESSING ORDER (ascending person id); the caller guarantees they are distinct.  A
+ * position TAKES PART when its row is inside [0, G) and holds a non-zero element (the sign bit does not count); any other position gets
+ * keeper -1, score 0, and for an entry outside [0, G) nothing is read or written.
+ * The rule, over positions k = 0 .. n - 1:  keeper[k] = the LOWEST position j < k with keeper[j] == -1 and hit(j, k), or -1 if there is none
+ * ("the first person still alive absorbs me", not "the best score"); hit = the rule of fid_gallery_range: the cosine of the two stored fp16
+ * unit rows, accumulated in fp32, is >= thresh and > 0 -- a zero (free / deleted) row and a NaN never hit.  Exact for any dependency depth.
+ * Outputs (device), by position: keeper_dev int32 [n]; score_dev float [n] = the cosine of position k with its keeper, 0 where keeper is -1;
+ * summary_dev int32 [2] = {positions absorbed, positions that took part}.
+ * apply != 0: after the last decision every absorbed row is set to all +0.0 (the state fid_gallery_set_rows leaves for a zero embedding); no
+ * other gallery byte is written.  apply == 0: the gallery is not written at all.
+ * The reference's merge list is the absorbed positions sorted by (keeper, -score, id): engine.merges_from_keepers.
+ * FID_E_INVALID, nothing enqueued, outputs untouched: a NULL pointer, n <= 0 or n > FID_DEDUP_MAX_ROWS, thresh NaN or <= 0, dim % 32 != 0.
+ * Asynchronous on the context's stream; no host synchronisation beyond the scratch-arena rule of fid_match (see fid_gallery_group).  Scratch:
+ * 12 bytes per position (no copy of the rows, no n x n or n x G matrix, no pair list). */
+#define FID_DEDUP_MAX_ROWS (1 << 20)
+int fid_gallery_dedup(fid_ctx *ctx, fid_gallery *g, const int32_t *rows_dev, int n, float thresh, int apply,
+                      int32_t *keeper_dev, float *score_dev, int32_t *summary_dev);
 /* Gallery sharded over ranks by contiguous row blocks (the 1 M-entry variant of main.py:136-142):
  * fid_match_keys scans THIS rank's rows (global index of its row 0 = first_row) for all n queries and writes one
  * packed key per query, (order-preserving bits of the score << 32) | ~global_index; after the ranks' key arrays

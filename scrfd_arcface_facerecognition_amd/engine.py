@@ -404,14 +404,28 @@ class VectorGallery:
         store: ids in ascending order; every id that is still stored absorbs all LARGER ids whose similarity reaches the threshold (their rows are
         deleted, as merge_duplicate_persons does through delete_embedding).  The G x G similarities come from the device in one pass (deletions only
         remove candidates, no embedding changes); the greedy pass over them is the reference's loop.  Returns [(kept id, deleted id, similarity)].
-        via="join": the same merges from the self-join's pair list (similar_pairs + merge_from_pairs) instead of the dense matrix."""
+        via="join": the same merges from the self-join's pair list (similar_pairs + merge_from_pairs) instead of the dense matrix.
+        via="device": the same merges from fid_gallery_dedup -- the greedy loop itself runs on the device, the absorbed rows are cleared there, and
+        ONE download of 8 bytes per person (keeper | score | summary) comes back; the host only sorts the merge list (merges_from_keepers) and does
+        delete()'s bookkeeping."""
+        if via == "device":
+            ids = sorted(self.row_of)
+            if not ids:
+                return []
+            keeper, score, _ = self._dedup_call(ids, similarity_threshold, apply=True)
+            merges = merges_from_keepers(ids, keeper, score)
+            for _, dead, _ in merges:                                   # delete([m[1] for m in merges]) without its device call
+                r = self.row_of.pop(dead)
+                self.id_of.pop(r)
+                self._free.append(r)
+            return merges
         if via == "join":
             merges = merge_from_pairs(list(self.row_of), self.similar_pairs(similarity_threshold), similarity_threshold)
             if merges:
                 self.delete([m[1] for m in merges])
             return merges
         if via != "matrix":
-            raise ValueError(f"find_and_merge_duplicates: via={via!r}, expected 'matrix' or 'join'")
+            raise ValueError(f"find_and_merge_duplicates: via={via!r}, expected 'matrix', 'join' or 'device'")
         ids = sorted(self.row_of)
         if len(ids) < 2:
             return []
@@ -434,6 +448,28 @@ class VectorGallery:
         if merges:
             self.delete([m[1] for m in merges])
         return merges
+
+    def _dedup_call(self, ids_sorted, threshold: float, apply: bool):
+        """fid_gallery_dedup on the rows of `ids_sorted` -> (keeper int32 [n], score fp32 [n], summary int32 [2]) on the host: one upload (the
+        rows), one call, one download (keeper | score | summary travel as ONE buffer)"""
+        n = len(ids_sorted)
+        if n > DEDUP_MAX_ROWS:
+            raise ValueError(f"find_and_merge_duplicates: {n} persons exceed the {DEDUP_MAX_ROWS} of one fid_gallery_dedup call; use via=\"join\"")
+        ctx = self.ctx
+        rows_dev = ctx.to_device(np.asarray([self.row_of[i] for i in ids_sorted], dtype=np.int32))
+        out = ctx.empty((2 * n + 2,), np.int32)
+        check(ctx.lib.fid_gallery_dedup(ctx.handle, self._gal.handle, C.c_void_p(rows_dev.ptr), n, C.c_float(threshold), 1 if apply else 0,
+                                        C.c_void_p(out.ptr), C.c_void_p(out.ptr + 4 * n), C.c_void_p(out.ptr + 8 * n)))
+        got = out.download()
+        return got[:n].copy(), got[n:2 * n].view(np.float32).copy(), got[2 * n:].copy()
+
+    def duplicate_keepers(self, threshold: float = 0.8):
+        """A dry run of find_and_merge_duplicates(via="device"): -> {deleted id: (kept id, score)}; neither the store nor the gallery changes."""
+        ids = sorted(self.row_of)
+        if not ids:
+            return {}
+        keeper, score, _ = self._dedup_call(ids, threshold, apply=False)
+        return {ids[k]: (ids[int(keeper[k])], float(score[k])) for k in np.nonzero(keeper >= 0)[0]}
 
 
     # ---- the visit loop (fid_gallery_group): a batch of visits grouped into persons in visit order, one call, one download ------------------------
@@ -654,6 +690,19 @@ def merge_from_pairs(ids, pairs, threshold: float):
             alive.discard(p2)
             merges.append((p1, p2, float(s)))
     return merges
+
+
+DEDUP_MAX_ROWS = 1 << 20                                                          # FID_DEDUP_MAX_ROWS
+
+
+def merges_from_keepers(ids_sorted, keeper, score):
+    """fid_gallery_dedup's answer as the reference's merge list: ids_sorted[k] is the id at position k (ascending), keeper[k] the position that
+    absorbed it or -1.  A keeper makes its merges when the loop reaches it, score-descending, then in ascending id order -- so the list is the
+    absorbed positions sorted by (keeper, -score, position).  Pure host code.  Returns [(kept id, deleted id, score)], as merge_from_pairs."""
+    keeper = np.asarray(keeper)
+    dead = [int(k) for k in np.nonzero(keeper >= 0)[0]]
+    dead.sort(key=lambda k: (int(keeper[k]), -float(score[k]), k))
+    return [(ids_sorted[int(keeper[k])], ids_sorted[k], float(score[k])) for k in dead]
 
 
 def _gallery_ptr(gal: Gallery) -> int:
