@@ -958,6 +958,9 @@ int gemm_launch(fid_ctx *ctx, ConvArgs a, const ConvPlan &plan, int gen, int ns)
     FID_REQUIRE(a.ksplit == 1 || a.partial, "conv: split-K without a partial buffer");
     const GemmTile *t = gemm_tile(gen, plan.bm, plan.bn, plan.bk, ns);
     FID_REQUIRE(t, "conv: no generation-%d implicit-GEMM kernel for tile %dx%dx%d ns=%d", gen, plan.bm, plan.bn, plan.bk, ns);
+    // FID_KLOG=1: the split as LAUNCHED (the heuristic plan of a net that does not autotune is in no plan table; tests/test_gpu_ops_exact.py)
+    static const bool klog = getenv("FID_KLOG") != nullptr;
+    if (klog) fprintf(stderr, "[klog] gemm gen %d tile %dx%dx%d ns %d: %d K-steps in %d slabs of %d\n", gen, plan.bm, plan.bn, plan.bk, ns, a.ksteps, a.ksplit, a.ksteps_per_split);
     FID_TRY(t->launch(ctx, a));
     if (a.ksplit > 1) {
         const long long n = (long long)a.M * (a.Cout_p / 4);

@@ -520,6 +520,7 @@ int run_op(fid_ctx *ctx, fid_net *net, int oi, const uint8_t *images, int first,
                 // workgroups per CU = what fits (64 couts: 146 VGPRs, three waves per SIMD; measured on IResNet's stem at 64 faces: 3 -> 33.9 us, 4 -> 39.8, 6 -> 39.3;
                 // without any load or store 29.4: the K gather and the fp32 epilogue are the time, not the 103 MB of output)
                 const int g = std::min(nt, ctx->num_cus * (dst.Cp == 128 ? 2 : (dst.Cp == 64 ? 3 : 4)));
+                if (klog) fprintf(stderr, "[klog] kernel stem_conv_mfma<%d, %d>\n", dst.Cp / 16, st);
 #define STEMM(NI, ST) hipLaunchKernelGGL((stem_conv_mfma<NI, ST>), dim3(g), dim3(256), 0, ctx->stream, images, w, bias, slope, (_Float16 *)dst.ptr, net->in_h, net->in_w, dst.H, dst.W, op[W_ACT], tx, ty, nt, abl)
                 if (dst.Cp == 128) { if (st == 1) STEMM(8, 1); else STEMM(8, 2); }            // (MobileFaceNet's first conv: 3 -> 128 channels, stride 2)
                 else if (dst.Cp == 64) { if (st == 1) STEMM(4, 1); else STEMM(4, 2); }
@@ -529,6 +530,7 @@ int run_op(fid_ctx *ctx, fid_net *net, int oi, const uint8_t *images, int first,
                 break;
             }
             static const int split = getenv("FID_STEM_SPLIT") ? atoi(getenv("FID_STEM_SPLIT")) : 2;   // measured on IResNet stem: 4 -> 107 us, 2 -> 91 us, 1 -> 102 us
+            if (klog) fprintf(stderr, "[klog] kernel stem_conv3x3 (Cout_p %d, stride %d)\n", dst.Cp, op[W_STRIDE]);
 #define STEM(CPW) hipLaunchKernelGGL(stem_conv3x3<CPW>, grid, dim3(256), 0, ctx->stream, images, w, bias, slope, (_Float16 *)dst.ptr, net->in_h, net->in_w, dst.H, dst.W, dst.Cp, op[W_STRIDE], op[W_ACT], total)
 #define STEMS(CPW, SP) hipLaunchKernelGGL((stem_conv3x3<CPW, SP>), dim3((unsigned)cdiv64(total, 64 * (4 / SP))), dim3(256), 0, ctx->stream, images, w, bias, slope, (_Float16 *)dst.ptr, net->in_h, net->in_w, dst.H, dst.W, dst.Cp, op[W_STRIDE], op[W_ACT], total)
             if (split == 1 && dst.Cp == 64) STEMS(64, 1);

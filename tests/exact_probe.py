@@ -1,4 +1,4 @@
-"""Bit-exact integer probes of the conv kernels (test_exact_probe_cpu.py, test_gpu_conv_exact.py).  Plain module, no fixtures.
+"""Bit-exact integer probes of the conv kernels (test_exact_probe_cpu.py, test_gpu_conv_exact.py, test_gpu_ops_exact.py).  Plain module, no fixtures.
 
 When every stored activation, weight, bias and PReLU slope of a layer is a small integer times a power of two, every fp16 x fp16 product and
 every partial sum of its convolution is exactly representable in fp32: the fp32 accumulator then holds the same number whatever the summation
@@ -12,6 +12,11 @@ reference that rounds every node to fp16 states it bit for bit -- for every kern
   check_exactness  the CONDITIONS under which the comparison may be exact and can see a fault, asserted on the reference alone
   assert_same_bits the comparator: finite, then equality of the fp16 values (+0 == -0), with positions / bit patterns / ulp histogram on failure
   PROBES           the probe nets: a 3 -> 64 stem, a 1x1 widening conv where the op needs more channels, then the op under test
+  split_mirror     the split-K plan a net that does not autotune launches (csrc/conv.hip conv_plan, FID_CONV_FORCE, gemm_launch), SPLIT_CASES
+
+Two node kinds besides convs: an FC (fold_fc, fc_columns, eval_fc: an fp32 tensor of exact sums on the activation's stored HWC order with padded
+channels; every K-step must change an output of every image, CHW-ordered columns must give another result) and a max pool (eval_pool: the
+source's grid; every window position is somewhere the strict maximum, and zero padding shows where the source is negative).
 
 BatchNorm with a zero running mean is in scope.  gamma / sqrt(var + eps) is no exact power of two, but exactness only needs the constants the
 device RECEIVES to be the ideal ones: with var = float32(1 - 1e-5) and gamma = +-2 ** k the scale is 2 ** k (1 + d), |d| < 2 ** -26, and the fp16
@@ -54,6 +59,17 @@ def int_params(net, seed, layers=None):
                 P[f"{n.wname}.{part}.bias"] = rng.integers(-64, 65, c).astype(np.float32)
             P[n.wname + ".bbox.scale"] = np.ones(1, np.float32)
             continue
+        if n.kind == "maxpool":
+            continue
+        if n.kind == "fc":                                    # integer weights [cout, c * h * w] (CHW columns, as the graph holds them) and biases
+            o = dict(density=1.0 / 3.0, mags=(1, 2), exp=0, bias=8)
+            o.update((layers or {}).get(n.name, {}))
+            shape = (n.cout, n.c * n.h * n.w)
+            w = rng.choice(o["mags"], shape) * rng.choice([-1, 1], shape) * (rng.random(shape) < o["density"])
+            P[n.wname + ".weight"] = (w * 2.0 ** o["exp"]).astype(np.float32)
+            if n.bias:
+                P[n.wname + ".bias"] = (rng.integers(-o["bias"], o["bias"] + 1, n.cout) * 2.0 ** o["exp"]).astype(np.float32)
+            continue
         assert n.kind == "conv", n.name                       # (a node's BatchNorms: bn_params)
         o = dict(density=1.0 if (n.src == "input" or n.groups > 1) else 1.0 / 3.0, mags=(1,) if n.src == "input" else (1, 2), exp=0, bias=8,
                  slopes=(0.5, 0.25))
@@ -80,12 +96,13 @@ def bn_params(net, seed, layers=None):
     rng = np.random.default_rng(seed)
     P = {}
     for n in net.nodes:
-        if n.kind != "conv":
+        if n.kind not in ("conv", "fc"):
             continue
-        for which, c in (("pre_bn", n.cin), ("post_bn", n.cout)):
+        for which, c in (("pre_bn", n.cin if n.kind == "conv" else n.c), ("post_bn", n.cout)):
             if not getattr(n, which):
                 continue
-            assert not n.bias, n.name                         # (bias a2 (1 + d) + beta2 would cancel: see the module docstring)
+            assert n.kind == "fc" or not n.bias, n.name       # (bias a2 (1 + d) + beta2 would cancel: see the module docstring; an FC's bias is
+                                                              #  summed with the shift of the BN in front BEFORE the scale, and its post-BN shift is 0)
             o = dict(scales=(1.0, 0.5), beta=8)
             o.update((layers or {}).get(f"{n.name}.{which}", {}))
             pre = f"{n.wname}.{which}"
@@ -147,8 +164,26 @@ def fold_node(n, P):
     return W, rows
 
 
-def int_images(seed, batch, hw):
-    return np.random.default_rng(seed).integers(PIXELS[0], PIXELS[1], (batch,) + tuple(hw) + (3,), dtype=np.uint8)
+def fold_fc(n, P):
+    """(W [cout, c, h, w], bias [cout]) of an FC node, float64: lower.py's fold stated again.  The BatchNorm in front scales the input channels
+    and its shift goes through every column into the bias; the BatchNorm behind scales the rows and shifts the bias."""
+    W = P[n.wname + ".weight"].astype(np.float64).reshape(n.cout, n.c, n.h, n.w)
+    b = P[n.wname + ".bias"].astype(np.float64) if n.bias else np.zeros(n.cout)
+    if n.pre_bn:
+        a1, b1 = ideal_affine(P, n.wname + ".pre_bn")
+        b = b + np.einsum("ochw,c->o", W, b1)
+        W = W * a1[None, :, None, None]
+    if n.post_bn:
+        a2, b2 = ideal_affine(P, n.wname + ".post_bn")
+        W = W * a2[:, None, None, None]
+        b = b * a2 + b2
+    return W, b
+
+
+def int_images(seed, batch, hw, pixels=None):
+    lo, hi = pixels or PIXELS
+    return np.random.default_rng(seed).integers(lo, hi, (batch,) + tuple(hw) + (3,), dtype=np.uint8)
+
 
 
 # ---- the exact reference -----------------------------------------------------------------------------------------------------------------
@@ -159,7 +194,7 @@ def _r16(y):
 
 
 def reference(net, P, images, raw=None):
-    """{node name: float64 [B, H, W, C] holding fp16 values} for every conv node.  raw: a dict that receives the values BEFORE the rounding"""
+    """{node name: float64 [B, H, W, C] holding fp16 values} for every conv and max-pool node ([B, cout] float64 for an FC).  raw: a dict that receives the values BEFORE the rounding"""
     out = {}
 
     def store(name, y):
@@ -172,19 +207,24 @@ def reference(net, P, images, raw=None):
 
     def bn(x, prefix):                                       # the ideal affine, not x / sqrt(var + eps): that lies 1e-9 off the grid and breaks ties
         a, b = ideal_affine(P, prefix)
-        return x * torch.from_numpy(a)[None, :, None, None] + torch.from_numpy(b)[None, :, None, None]
+        sh = (1, -1) + (1,) * (x.dim() - 2)                   # ([B, C, H, W], or [B, C] behind an FC)
+        return x * torch.from_numpy(a).view(sh) + torch.from_numpy(b).view(sh)
 
     blob = align.blob_from_images(list(images), net.in_scale, net.in_mean)
     res = onets.run_net(net, P, blob, keep=[n.name for n in net.nodes], dtype=torch.float64, store=store, bn=bn)
     for n in net.nodes:
         if n.kind == "dethead":                               # an fp32 tensor on the device: (scores, bbox, kps) as float64, not rounded
             out[n.name] = res[n.name]
+        elif n.kind == "fc":                                  # fp32 as well: [B, cout] exact sums
+            out[n.name] = res[n.name]
+            if raw is not None:
+                raw[n.name] = res[n.name]
     out["input"] = np.transpose(blob, (0, 2, 3, 1)).astype(np.float64)
     return out
 
 
 def _nchw(a):
-    return torch.from_numpy(np.ascontiguousarray(np.transpose(a, (0, 3, 1, 2))))
+    return torch.from_numpy(np.array(np.transpose(a, (0, 3, 1, 2)), order="C"))       # (always a copy: the cached references are read-only)
 
 
 def _chunks(n):
@@ -204,7 +244,7 @@ def _chunks(n):
     return masks
 
 
-def eval_node(n, ref, P, mode="exact", rounded=True):
+def eval_node(n, ref, P, mode="exact", rounded=True, arg=None):
     """One conv node from the reference's STORED inputs, [B, H, W, C] as float64 holding fp16 values, in its FOLDED form (fold_node: the weights
     and the bias row of every pixel's border class, as the device computes it; the reference applies the BatchNorms as they stand).  mode:
       exact          float64, one conv
@@ -215,20 +255,37 @@ def eval_node(n, ref, P, mode="exact", rounded=True):
       fault_rtz      the store rounds toward zero
       fault_border   every pixel takes the interior bias row (a node with border classes)
       fault_class    the top-left corner pixel of the LAST image takes the top-edge row
+      fault_kstep    a split-K slab loses one K-step: arg = (bk, Cin_p, step), the columns [step bk, (step + 1) bk) of the (tap, stored channel) axis
+      fault_bias_slabs  the bias row is added once per slab: arg = the number of slabs
+      fault_row      kernel row `arg` of every filter is missing (the global depthwise conv's row lanes)
     rounded=False: the float64 value before the store (the f32 modes always return the fp32 accumulator's value)"""
     dt = torch.float32 if mode.startswith("f32") else torch.float64
     x = _nchw(ref[n.src]).to(dt)
     if n.pre_avgpool:
         x = F.avg_pool2d(x, 2, 2)
     wf, rows = fold_node(n, P)
+    if mode == "fault_kstep":
+        bk, cin_p, step = arg
+        assert n.groups == 1 and not n.pre_avgpool and (step + 1) * bk <= n.k * n.k * cin_p, (n.name, arg)
+        wf = wf.copy()
+        for col in range(step * bk, (step + 1) * bk):
+            tap, ci = divmod(col, cin_p)
+            if ci < wf.shape[1]:                              # (a padded channel multiplies a zero weight anyway)
+                wf[:, ci, tap // n.k, tap % n.k] = 0
+    elif mode == "fault_bias_slabs":
+        rows = rows * arg
+    elif mode == "fault_row":
+        wf = wf.copy()
+        wf[:, :, arg, :] = 0
     w = torch.from_numpy(wf).to(dt)
     conv = lambda xx, ww: F.conv2d(xx, ww, None, n.stride, n.pad, 1, n.groups)
-    if mode in ("exact", "fault_rtz", "fault_border", "fault_class"):
+    if mode in ("exact", "fault_rtz", "fault_border", "fault_class", "fault_kstep", "fault_bias_slabs", "fault_row"):
         y = conv(x, w)
     elif mode == "fault_tap":
         y = conv(x, w)
         x0 = torch.zeros_like(x)
-        x0[0, :, 0, 0] = x[0, :, 0, 0]
+        at = n.k // 2 - n.pad                                 # the input pixel under the centre tap of output pixel (0, 0): (0, 0) where the conv pads
+        x0[0, :, at, at] = x[0, :, at, at]
         w0 = torch.zeros_like(w)
         w0[:, :, n.k // 2, n.k // 2] = w[:, :, n.k // 2, n.k // 2]
         y = y - conv(x0, w0)                                  # (that product only reaches output pixel (0, 0) of image 0)
@@ -314,6 +371,15 @@ def check_exactness(net, P, images, probed, onchip=(), ref=None, raw=None):
     for n in net.nodes:
         if n.kind == "dethead":
             stats[n.name] = _check_dethead(n, P, ref, grid[n.src])
+            continue
+        if n.kind == "fc":
+            stats[n.name] = _check_fc(n, P, ref, grid[n.src])
+            continue
+        if n.kind == "maxpool":                               # a selection: the source's grid, no sum, no rounding
+            grid[n.name] = grid[n.src]
+            assert np.array_equal(raw[n.name], ref[n.name]) and np.isfinite(ref[n.name]).all(), n.name
+            if n.name in probed:
+                stats[n.name] = _check_pool(n, ref, grid[n.src])
             continue
         w, b = fold_node(n, P)                                # through both BatchNorms: the folded weights W a1 a2 and the bias rows
         if n.pre_bn or n.post_bn:
@@ -415,6 +481,130 @@ def _check_dethead(n, P, ref, g_src):
     return st
 
 
+def fc_columns(n, ref, P, order="hwc"):
+    """(x [B, K], W [cout, K], bias [cout]) of an FC node as the device multiplies them, float64: K = h w Cp, the activation's stored HWC order
+    with the channels padded to a multiple of 32 (zeros on both sides).  order="chw": the weight columns left in the graph's CHW order
+    (a lowering that forgot the permutation; Cp = c only)."""
+    W4, b = fold_fc(n, P)
+    x = ref[n.src]                                            # [B, h, w, c]
+    B, cp = x.shape[0], (n.c + 31) // 32 * 32
+    xk = np.zeros((B, n.h, n.w, cp))
+    xk[..., :n.c] = x
+    Wk = np.zeros((n.cout, n.h, n.w, cp))
+    if order == "chw":
+        assert cp == n.c
+        Wk = W4.reshape(n.cout, -1)
+    else:
+        Wk[..., :n.c] = W4.transpose(0, 2, 3, 1)
+    return xk.reshape(B, -1), Wk.reshape(n.cout, -1), b
+
+
+def fc_bk(n):
+    """the K-step of the implicit GEMM on the FC's flattened input (csrc/conv.hip conv_plan: 64 where the row length allows it)"""
+    K = n.h * n.w * ((n.c + 31) // 32 * 32)
+    return 64 if K % 64 == 0 else 32
+
+
+def eval_fc(n, ref, P, mode="exact", arg=None):
+    """One FC node from the reference's stored input, in its folded form and the device's column order; [B, cout] float64.  mode:
+      exact          float64
+      f32_fwd / f32_rev   float32, K-step by K-step (fc_bk columns each), first to last / last to first
+      chw            the weight columns in CHW order
+      fault_kstep    K-step `arg` is missing (a slab that drops a step)
+      fault_kstep_twice   K-step `arg` is added twice (two slabs that overlap)
+      fault_bias_slabs    the bias is added once per slab: arg = the number of slabs"""
+    x, W, b = fc_columns(n, ref, P, "chw" if mode == "chw" else "hwc")
+    bk = fc_bk(n)
+    if mode in ("f32_fwd", "f32_rev"):
+        steps = list(range(x.shape[1] // bk))
+        y = np.zeros((x.shape[0], n.cout), np.float32)
+        for s_ in (steps if mode == "f32_fwd" else steps[::-1]):
+            y = y + x[:, s_ * bk:(s_ + 1) * bk].astype(np.float32) @ W[:, s_ * bk:(s_ + 1) * bk].astype(np.float32).T
+        return y + b.astype(np.float32)
+    y = x @ W.T + b
+    if mode in ("fault_kstep", "fault_kstep_twice"):
+        part = x[:, arg * bk:(arg + 1) * bk] @ W[:, arg * bk:(arg + 1) * bk].T
+        y = y - part if mode == "fault_kstep" else y + part
+    elif mode == "fault_bias_slabs":
+        y = y + b * (arg - 1)
+    else:
+        assert mode in ("exact", "chw"), mode
+    return y
+
+
+def _check_fc(n, P, ref, g_src):
+    """an FC node: an fp32 store of exact sums (grid, partial sums, coverage), and the two conditions that give the comparison power over a
+    split-K plan and over the column order: every K-step changes some output of EVERY image, and CHW-ordered columns give another result"""
+    W4, b = fold_fc(n, P)
+    assert _is_f16(W4).all() and (np.abs(b) < 2.0 ** 24).all(), (n.name, "folded weights are not fp16 values")
+    g = min(g_src * lsb_of(W4), lsb_of(b))
+    x, W, _ = fc_columns(n, ref, P)
+    assert _on_grid(ref[n.src], g_src) and np.isfinite(x).all(), n.name
+    S = np.abs(x) @ np.abs(W).T + np.abs(b)
+    bits = float(np.log2(S.max() / g))
+    assert 2.0 ** -24 <= g <= 1.0 and S.max() / g < GUARD, (n.name, g, bits)
+    y = ref[n.name]
+    assert y.shape == (x.shape[0], n.cout) and np.array_equal(y, eval_fc(n, ref, P)), n.name     # (the fold IS the BatchNorms as they stand)
+    assert _on_grid(y, g) and np.array_equal(y.astype(np.float32).astype(np.float64), y), n.name
+    assert (y != 0).mean() >= 0.20 and (np.abs(W).sum(axis=0)[np.abs(x).sum(axis=0) > 0] > 0).all(), n.name
+    bk = fc_bk(n)
+    steps = x.shape[1] // bk
+    assert steps * bk == x.shape[1]
+    part = np.einsum("bsk,osk->bso", x.reshape(x.shape[0], steps, bk), W.reshape(n.cout, steps, bk))
+    dead = np.argwhere(~(part != 0).any(axis=2))
+    assert dead.size == 0, (n.name, "a K-step that changes no output of an image (image, step)", dead[:4].tolist())
+    if (n.c + 31) // 32 * 32 == n.c:
+        assert (eval_fc(n, ref, P, "chw") != y).mean() >= 0.5, (n.name, "CHW-ordered columns give the same result")
+    return dict(grid=g, sum_bits=bits, max=float(np.abs(y).max()), nonzero=float((y != 0).mean()), ksteps=steps, bk=bk,
+                outputs_per_step=float((part != 0).mean()))
+
+
+def eval_pool(n, ref, mode="exact", arg=None):
+    """One max-pool node from the reference's stored input; [B, Ho, Wo, C] float64.  mode:
+      exact      taps outside the map are ignored
+      fault_pad0 the map is padded with 0 and every tap counts
+      fault_row_off   output row `arg` is taken one input row further down (a pooled row from the wrong tile at a seam)"""
+    x = _nchw(ref[n.src])
+    y = F.max_pool2d(x, n.k, n.stride, n.pad)
+    if mode == "fault_pad0":
+        y = F.max_pool2d(F.pad(x, (n.pad,) * 4, value=0.0), n.k, n.stride, 0)
+    elif mode == "fault_row_off":
+        down = torch.cat([x[:, :, 1:], torch.full_like(x[:, :, :1], -np.inf)], dim=2)
+        y = y.clone()
+        y[:, :, arg] = F.max_pool2d(down, n.k, n.stride, n.pad)[:, :, arg]
+    else:
+        assert mode == "exact", mode
+    return y.permute(0, 2, 3, 1).numpy()
+
+
+def _check_pool(n, ref, g_src):
+    """a max pool: each of the k x k window positions is the STRICT maximum of some interior output and channel (a tap that is never read
+    shows), and where the source has negative values, padding with 0 instead of ignoring the taps outside changes a border output"""
+    x = _nchw(ref[n.src])
+    assert np.array_equal(eval_pool(n, ref), ref[n.name]) and _on_grid(ref[n.name], g_src), n.name
+    off = -(-n.pad // n.stride) * n.stride - n.pad            # the first window that lies inside the map
+    inner = x[:, :, off:, off:]
+    B, C = inner.shape[:2]
+    win = F.unfold(inner, n.k, stride=n.stride).view(B, C, n.k * n.k, -1)
+    top = win.max(dim=2, keepdim=True).values
+    strict = (win == top) & ((win == top).sum(dim=2, keepdim=True) == 1)
+    won = strict.any(dim=3).any(dim=1).any(dim=0).numpy()
+    assert won.all(), (n.name, "window positions that never hold the strict maximum", np.flatnonzero(~won).tolist())
+    st = dict(grid=g_src, positions=float(strict.float().sum(dim=2).mean()), negative=float((ref[n.src] < 0).mean()))
+    if (ref[n.src] < 0).any() and n.pad > 0:
+        bad = eval_pool(n, ref, "fault_pad0") != ref[n.name]
+        Ho, Wo = bad.shape[1:3]
+        H, W = ref[n.src].shape[1:3]
+        clipped = np.zeros((Ho, Wo), bool)
+        for oy in range(Ho):
+            for ox in range(Wo):
+                clipped[oy, ox] = (oy * n.stride - n.pad < 0 or ox * n.stride - n.pad < 0 or oy * n.stride - n.pad + n.k > H
+                                   or ox * n.stride - n.pad + n.k > W)
+        assert bad[:, clipped].any() and not bad[:, ~clipped].any(), (n.name, "zero padding changes no border output")
+        st["pad0_changes"] = float(bad[:, clipped].mean())
+    return st
+
+
 def _no_act(n):
     import dataclasses
     return dataclasses.replace(n, act="none")
@@ -452,8 +642,8 @@ def assert_same_values(got, ref, what=""):
     assert np.isfinite(got).all() and np.isfinite(ref).all(), f"{what}: not finite"
     bad = np.argwhere(got != ref)
     if len(bad):
-        i = tuple(bad[0])
-        raise AssertionError(f"{what}: {len(bad)} of {got.size} values differ; first at {i}: got {got[i]!r} ref {ref[i]!r}")
+        i = tuple(int(v) for v in bad[0])
+        raise AssertionError(f"{what}: {len(bad)} of {got.size} values differ; first at {i}: got {float(got[i])!r} ref {float(ref[i])!r}")
 
 
 # ---- the probe nets ----------------------------------------------------------------------------------------------------------------------
@@ -467,6 +657,7 @@ class Probe:
     probed: List[str]                        # nodes compared bit for bit whose conditions check_exactness asserts
     onchip: List[str] = field(default_factory=list)     # nodes a fused op keeps on chip
     env: Dict[str, str] = field(default_factory=dict)
+    through: List[str] = field(default_factory=list)    # nodes held to the probed nodes' conditions that a fused form only shows through a later node
 
     @property
     def batch(self):
@@ -771,3 +962,190 @@ IR_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(ir_probe), *sh) for s
 SHORTCUT_BN_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(shortcut_bn_probe), *sh) for sh in SHORTCUT_SHAPES}
 STEM_BN_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(stem_bn_probe), *sh) for sh in STEM_SHAPES}
 BN_KEYS = sorted(list(FAMILY_BN_KEYS.values()) + list(IR_KEYS.values()) + list(SHORTCUT_BN_KEYS.values()) + list(STEM_BN_KEYS.values()))
+
+
+# ---- the split-K plan of the implicit GEMM, mirrored ---------------------------------------------------------------------------------------
+# What a net that does not autotune (FID_AUTOTUNE=0) launches for a conv the direct kernel does not take: csrc/conv.hip conv_plan's generation-2
+# branch, its FID_CONV_FORCE="bm,bn,ksplit" hook, and gemm_launch's recomputation of the split count from whole K-steps per slab.
+# tests/test_exact_probe_cpu.py holds it against the library's own conv_plan on a grid of shapes; tests/test_gpu_ops_exact.py against what runs.
+
+GEMM2_TILES = {64: ((128, 128), (128, 64), (64, 64)), 32: ((128, 128), (128, 96), (128, 64), (128, 32))}      # GEMM_TILES, generation 2, four ring slots
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def split_mirror(M, cin_p, cout_p, taps, cus, force=None, allow_split=True):
+    """dict(bm, bn, bk, ksteps, ksplit = the plan's split count, per = K-steps per slab, slabs = the K-steps of every launched slab).
+    force: FID_CONV_FORCE as (bm, bn, ksplit)."""
+    bk = 64 if cin_p % 64 == 0 else 32
+    tiles = lambda bm, bn: _cdiv(M, bm) * _cdiv(cout_p, bn)
+    bm = 128
+    bn = 128 if cout_p % 128 == 0 else 96 if cout_p % 96 == 0 else 128 if cout_p > 64 else 64 if cout_p > 32 else 32
+    if tiles(bm, bn) < cus and bn == 128:
+        bn = 64
+    if tiles(bm, bn) < cus and bn == 64 and bk == 64:
+        bm = 64
+    if bk == 64 and bn not in (128, 64):
+        bn = 128 if cout_p > 64 else 64
+    ksteps = _cdiv(taps * cin_p, bk)
+    t, ks = tiles(bm, bn), 1
+    if allow_split and t * 2 <= cus and ksteps >= 16:
+        ks = max(1, min(_cdiv(cus, t), ksteps // 8))
+    if force is not None:
+        fbm, fbn, fks = force
+        if (fbm, fbn) in GEMM2_TILES[bk]:
+            bm, bn = fbm, fbn
+        if fks >= 1 and allow_split:
+            ks = max(1, min(fks, ksteps // 2))
+    per = _cdiv(ksteps, ks)                                   # gemm_launch: whole K-steps per slab, then the slabs that are not empty
+    n = _cdiv(ksteps, per)
+    return dict(bm=bm, bn=bn, bk=bk, ksteps=ksteps, ksplit=ks, per=per, slabs=[min(per, ksteps - i * per) for i in range(n)])
+
+
+def conv_geometry(low, name, batch):
+    """(M, Cin_p, Cout_p, taps) of the OP_CONV record `name` of a lowered net, as csrc/net.hip run_op hands them to conv_plan"""
+    r = low.ops[low.op_names.index(name)]
+    src, dst = low.tensors[int(r[1])], low.tensors[int(r[2])]
+    return batch * int(dst[2]) * int(dst[3]), int(src[1]), int(dst[1]), int(r[4]) * int(r[5])
+
+
+def takes_gdc_rows(low, name):
+    """csrc/net.hip OP_DWCONV: the record `name` meets the condition under which gdc_rows runs instead of dwconv_nhwc"""
+    r = low.ops[low.op_names.index(name)]
+    src, dst = low.tensors[int(r[1])], low.tensors[int(r[2])]
+    return (int(r[0]) == 4 and int(r[4]) == int(r[5]) <= 8 and int(r[7]) == 0 and int(src[2]) == int(r[4]) and int(src[3]) == int(r[5])
+            and int(dst[2]) == 1 and int(dst[3]) == 1)
+
+
+# ---- split-K probes: the family nets under a forced split, and a 1x1 conv with an up-sampled residual ---------------------------------------
+
+def up2_probe(hw, cin, cout, batch):
+    """a 1x1 conv on `cin` channels that adds a map of half the size, up-sampled (CF_RES_UP2), PReLU: with cin = 1024 its K axis is 16 steps of
+    64, which the heuristic plan already splits"""
+    net = _net(hw)
+    net.add(Conv("s", "input", 3, 64, act="relu", **KW))
+    net.add(Conv("x", "s", 64, cin, k=1, pad=0, act="relu", **KW))
+    net.add(Conv("d", "s", 64, cout, stride=2, **KW))
+    net.add(Conv("u", "x", cin, cout, k=1, pad=0, act="prelu", res="d", res_up2=True, **KW))
+    net.outputs = ["x", "d", "u"]
+    layers = {"s": dict(density=1.0 / 3.0), "x": dict(density=8.0 / 64, mags=(1,)), "d": dict(density=4.0 / 576, mags=(1,)),
+              "u": dict(density=1.0 / 8.0, mags=(1, 2, 3, 4, 5, 6, 7), bias=64)}
+    return Probe(f"up2-{hw[0]}x{hw[1]}-{cin}-{cout}x{batch}", net, int_params(net, 37, layers), int_images(18, batch, hw), ["u"])
+
+
+UP2_SHAPES = [((8, 8), 1024, 56, 3)]
+UP2_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(up2_probe), *sh) for sh in UP2_SHAPES}
+
+# (probe key, node names, FID_CONV_FORCE, the K-steps of every slab) -- the slabs follow from the forced split alone, whatever the device
+SPLIT_CASES = [
+    (FAMILY_KEYS[((14, 14), 128, 128, 5)], ("c", "r"), "128,64,2", [9, 9]),                     # 3x3 on 128 channels: 18 steps of 64
+    (FAMILY_KEYS[((14, 14), 128, 128, 5)], ("c", "r"), "64,64,9", [2] * 9),                     # fewer steps than the ring's prologue
+    (FAMILY_KEYS[((14, 14), 128, 128, 5)], ("c", "r"), "128,128,4", [5, 5, 5, 3]),              # a ragged last slab
+    (FAMILY_KEYS[((14, 14), 128, 128, 5)], ("c", "r"), "128,64,7", [3] * 6),                    # a request the launcher reduces: 7 -> 6 slabs
+    (FAMILY_KEYS[((40, 24), 88, 224, 2)], ("c",), "128,64,7", [4] * 6 + [3]),                   # 96 stored channels: 27 steps of 32, three per tap; slabs begin inside a tap
+    (FAMILY_KEYS[((40, 24), 88, 224, 2)], ("c", "r"), "128,128,2", [14, 13]),
+    (FAMILY_BN_KEYS[((3, 5), 64, 64, 7)], ("c", "r"), "64,64,4", [3, 3, 3]),                    # border-class bias rows behind the slab sum
+    (FAMILY_BN_KEYS[((3, 5), 64, 64, 7)], ("c", "r"), "128,64,2", [5, 4]),
+    (UP2_KEYS[UP2_SHAPES[0]], ("u",), None, None),                                              # the heuristic's own split (by the device's CU count)
+    (UP2_KEYS[UP2_SHAPES[0]], ("u",), "64,64,5", [4, 4, 4, 4]),                                 # up-sampled residual behind the slab sum
+]
+
+
+# ---- FC ----------------------------------------------------------------------------------------------------------------------------------------
+
+def fc_probe(c, hw_map, cout, batch):
+    """IResNet's last op on a small map: stem, [1x1 to c channels], two 3x3 / stride-2 convs down to the map, BN - FC - BN with a bias"""
+    from scrfd_arcface_facerecognition_amd.archs import FC
+    h, w = hw_map
+    net = _net((4 * h, 4 * w))
+    net.add(Conv("s", "input", 3, 64, act="relu", **KW))
+    x = "s"
+    if c != 64:
+        x = net.add(Conv("x", "s", 64, c, k=1, pad=0, act="relu", **KW))
+    net.add(Conv("a", x, c, c, stride=2, act="relu", **KW))
+    net.add(Conv("b", "a", c, c, stride=2, **KW))
+    net.add(FC("fc", "b", c, h, w, cout))
+    net.outputs = ["b", "fc"]
+    few = lambda taps: dict(density=4.0 / taps, mags=(1,))
+    layers = {"s": dict(density=1.0 / 3.0), "x": few(64), "a": few(9 * c), "b": few(9 * c), "fc": dict(density=1.0 / 4.0, mags=(1, 2), bias=64)}
+    P = int_params(net, 41, layers)
+    P.update(bn_params(net, 42))
+    return Probe(f"fc-{c}x{h}x{w}-{cout}x{batch}", net, P, _narrow_images(19, batch, net.in_hw), ["fc"])
+
+
+FC_SHAPES = [(64, (5, 5), 512, 1), (64, (5, 5), 512, 3), (64, (5, 5), 512, 130), (128, (7, 7), 512, 2), (88, (5, 5), 128, 3)]
+FC_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(fc_probe), *sh) for sh in FC_SHAPES}
+
+
+# ---- the fused detector stem -----------------------------------------------------------------------------------------------------------------
+# conv / stride 2 - conv - conv - max pool 3 / 2 / 1, all ReLU.  Every form of it (csrc/stem_rows.hip with 8 or 6 pooled rows and with wave roles,
+# csrc/stem_fused.hip) keeps stem.0 and stem.1 in LDS as fp16, rounded from the fp32 accumulator exactly as the unfused convs store them
+# (__builtin_convertvector to half, ReLU after the rounding: the same bits), and rounds stem.2 once: the row kernels pool the fp32 accumulators and
+# round the maximum, the flat kernel rounds and then pools -- rounding is monotone, so both are max(round(.)).  The reference therefore rounds
+# all three maps and nothing is listed as kept on chip; stem.2 is held to the power conditions and seen through the pool.
+
+def stemfused_probe(hw, c0, c2, batch):
+    from scrfd_arcface_facerecognition_amd.archs import MaxPool
+    net = _net(hw)
+    net.add(Conv("stem.0", "input", 3, c0, stride=2, act="relu", **KW))
+    net.add(Conv("stem.1", "stem.0", c0, c0, act="relu", **KW))
+    net.add(Conv("stem.2", "stem.1", c0, c2, act="relu", **KW))
+    net.add(MaxPool("stem.pool", "stem.2", c2))
+    net.outputs = ["stem.pool"]
+    layers = {"stem.1": dict(density=1.0 / 3.0, mags=(1, 2), exp=-4, bias=64), "stem.2": dict(DENSE)}
+    return Probe(f"stemfused-{hw[0]}x{hw[1]}-{c0}-{c2}x{batch}", net, int_params(net, 43, layers), int_images(20, batch, hw), ["stem.pool"],
+                 through=["stem.2"])
+
+
+STEMFUSED_SHAPES = [((72, 100), 12, 24, 2), ((64, 64), 28, 56, 3), ((100, 76), 24, 24, 3)]
+STEMFUSED_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(stemfused_probe), *sh) for sh in STEMFUSED_SHAPES}
+
+
+# ---- the first conv of a net on its own ---------------------------------------------------------------------------------------------------------
+# 27 taps: the whole pixel range (|2 p - 255| <= 255) and factors up to 7 make most sums need rounding; at most 27 * 255 * 7 + 64 < 65504.
+
+def first_probe(hw, cout, stride, batch):
+    net = _net(hw)
+    net.add(Conv("s", "input", 3, cout, stride=stride, act="prelu" if stride == 2 else "relu", **KW))
+    net.outputs = ["s"]
+    P = int_params(net, 45, {"s": dict(mags=(1, 2, 3, 4, 5, 6, 7), bias=64)})
+    return Probe(f"first-{hw[0]}x{hw[1]}-{cout}s{stride}x{batch}", net, P, int_images(21, batch, hw, (0, 256)), ["s"])
+
+
+FIRST_SHAPES = [(hw, cout, st, 2) for hw in ((36, 52), (36, 50)) for cout in (12, 28, 64, 128) for st in (1, 2)]
+FIRST_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(first_probe), *sh) for sh in FIRST_SHAPES}
+
+
+# ---- max pool and the global depthwise conv ------------------------------------------------------------------------------------------------------
+
+def pool_probe(hw, c, batch):
+    """max pool 3 / 2 / 1 behind a PReLU conv: negative values, so a tap outside the map that counted as 0 would win at the border"""
+    from scrfd_arcface_facerecognition_amd.archs import MaxPool
+    net = _net(hw)
+    net.add(Conv("s", "input", 3, c, act="prelu", **KW))
+    net.add(MaxPool("pool", "s", c))
+    net.outputs = ["s", "pool"]
+    return Probe(f"pool-{hw[0]}x{hw[1]}-{c}x{batch}", net, int_params(net, 47, {"s": dict(bias=64)}), int_images(22, batch, hw), ["pool"])
+
+
+def gdc_probe(k, c, batch, act):
+    """MobileFaceNet's global depthwise conv: k x k, no padding, on a k x k map (csrc/net.hip gdc_rows: lane r of eight sums kernel row r)"""
+    net = _net((k, k))
+    net.add(Conv("s", "input", 3, 64, act="relu", **KW))
+    x = "s"
+    if c != 64:
+        x = net.add(Conv("x", "s", 64, c, k=1, pad=0, act="relu", **KW))
+    net.add(Conv("g", x, c, c, k=k, pad=0, groups=c, act=act, **KW))
+    net.outputs = [x, "g"]
+    layers = {"s": dict(density=1.0 / 3.0 if c != 64 else 1.0), "x": dict(density=8.0 / 64, mags=(1,)), "g": dict(FINE)}       # (k k taps on integers: quarters, so that most sums need rounding)
+    return Probe(f"gdc-{k}x{k}-{c}-{act}x{batch}", net, int_params(net, 49, layers), int_images(23, batch, (k, k)), ["g"])
+
+
+POOL_SHAPES = [((37, 21), 56, 3), ((16, 16), 56, 3), ((37, 21), 24, 3), ((16, 16), 24, 3)]
+GDC_SHAPES = [(7, 512, 1, "prelu"), (7, 512, 3, "none"), (7, 512, 5, "prelu"), (7, 128, 1, "none"), (5, 64, 3, "prelu")]
+POOL_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(pool_probe), *sh) for sh in POOL_SHAPES}
+GDC_KEYS = {sh: _register(functools.lru_cache(maxsize=None)(gdc_probe), *sh) for sh in GDC_SHAPES}
+OPS_KEYS = sorted(list(UP2_KEYS.values()) + list(FC_KEYS.values()) + list(STEMFUSED_KEYS.values()) + list(FIRST_KEYS.values())
+                  + list(POOL_KEYS.values()) + list(GDC_KEYS.values()))

@@ -4,6 +4,7 @@ comparator sees three planted faults on every probe net; ReLU before and after t
 BatchNorm (exact_probe.BN_KEYS): a wrong border class shows at every border pixel, and lowering them yields the constants of the ideal affine
 byte for byte, which is what lets the GPU module compare them without a tolerance."""
 import dataclasses
+import os
 
 import numpy as np
 import pytest
@@ -11,20 +12,27 @@ import pytest
 import exact_probe as ep
 
 KEYS = sorted(ep.PROBES)
-CONV_KEYS = [k for k in KEYS if ep.PROBES[k]().probed]      # (the detector head probes store fp32: no rounding to plant a fault in)
+
+
+def _held(probe):
+    """the conv nodes held to the probed nodes' conditions (an FC or a max pool has its own checks below)"""
+    return [n for n in probe.net.nodes if n.name in probe.probed + probe.through and n.kind == "conv"]
+
+
+CONV_KEYS = [k for k in KEYS if _held(ep.PROBES[k]())]      # (the detector head and FC probes store fp32: no rounding to plant a fault in)
 
 
 def _probed(key):
     probe = ep.PROBES[key]()
     ref, raw = ep.cached_reference(key)
-    return probe, ref, raw, [n for n in probe.net.nodes if n.name in probe.probed]
+    return probe, ref, raw, _held(probe)
 
 
 @pytest.mark.parametrize("key", KEYS)
 def test_probe_conditions(key):
     probe, ref, raw, nodes = _probed(key)
-    stats = ep.check_exactness(probe.net, probe.P, probe.images, probe.probed, probe.onchip, ref, raw)
-    assert set(probe.probed) | set(probe.onchip) <= set(stats) and len(stats) > 0
+    stats = ep.check_exactness(probe.net, probe.P, probe.images, probe.probed + probe.through, probe.onchip, ref, raw)
+    assert set(probe.probed) | set(probe.through) | set(probe.onchip) <= set(stats) and len(stats) > 0
     for n in nodes:                                          # the one-node evaluator the checks below plant their faults in IS the reference
         ep.assert_same_bits(ep.eval_node(n, ref, probe.P), ref[n.name], f"{key} / {n.name}")
 
@@ -165,3 +173,187 @@ def test_comparator_details():
 
 def test_lsb_tracking():
     assert ep.lsb_of([3.0, -6.0, 0.0]) == 1.0 and ep.lsb_of([0.75, 4.0]) == 0.25 and ep.lsb_of([48.0]) == 16.0 and ep.lsb_of([0.0]) == 1.0
+
+
+# ---- split-K, FC, the fused detector stem, the first conv, max pool and GDC (tests/test_gpu_ops_exact.py) ------------------------------------
+
+from test_conv_variants_cpu import HIPCC, LIB, driver, run      # noqa: E402,F401  (the host-only driver of the library's dispatch functions)
+
+needs_driver = pytest.mark.skipif(not (os.path.exists(HIPCC) and os.path.exists(LIB)), reason="needs hipcc and the built libfaceid.so")
+
+
+@needs_driver
+@pytest.mark.parametrize("force", [None, "128,64,2", "64,64,9", "128,128,4", "128,64,7", "128,96,5", "128,32,3"])
+def test_split_mirror_is_conv_plan(driver, force):
+    """exact_probe.split_mirror against the library's conv_plan (the driver's "h1" / "h0" lines: the heuristic pick with and without split-K at
+    256 CUs) on every plain shape of the driver's grid, with and without FID_CONV_FORCE"""
+    lines = run(driver, ["grid", "-v"], {"FID_CONV_FORCE": force} if force else {})
+    f = tuple(int(v) for v in force.split(",")) if force else None
+    seen = split = 0
+    for i, line in enumerate(lines):
+        if not line.startswith("shape "):
+            continue
+        w = line.split()
+        a = dict(zip(w[1::2], (int(v) for v in w[2::2])))
+        if a["out2"] or a["T2"]:                             # (the fused shortcut forms take other branches of conv_plan)
+            continue
+        j = i + 1
+        while not lines[j].startswith("h1 "):
+            j += 1
+        for tag, allow, row in (("h1", True, lines[j]), ("h0", False, lines[j + 1])):
+            v = row.split()
+            assert v[0] == tag
+            gen, bm, bn, bk, ks = (int(x) for x in v[1:6])
+            m = ep.split_mirror(a["M"], a["Cin"], a["Cout"], a["k"] * a["k"], 256, f, allow)
+            assert (gen, bm, bn, bk, ks) == (2, m["bm"], m["bn"], m["bk"], m["ksplit"]), (line, row, m)
+            assert int(v[7]) == (ks * a["M"] * a["Cout"] * 4 if ks > 1 else 0)
+            seen += 1
+            split += ks > 1
+    assert seen > 10000 and split > 1000
+
+
+SPLIT_IDS = [f"{k}-{f}" for k, _, f, _ in ep.SPLIT_CASES]
+
+
+def _split_geometry(key, name, monkeypatch):
+    from scrfd_arcface_facerecognition_amd import lower
+    probe = ep.PROBES[key]()
+    low = lower.lower(probe.net, probe.P)
+    assert int(low.ops[low.op_names.index(name)][0]) == lower.OP_CONV
+    return probe, low, ep.conv_geometry(low, name, probe.batch)
+
+
+@pytest.mark.parametrize("key,names,force,slabs", ep.SPLIT_CASES, ids=SPLIT_IDS)
+def test_split_cases_split_as_they_say(key, names, force, slabs, monkeypatch):
+    """the slabs every split-K case is about follow from its FID_CONV_FORCE through the mirror (whatever the CU count), the probed ops carry the
+    epilogue features the case names, and a dropped K-step, a K-step of the LAST slab, and a bias added once per slab change the reference"""
+    from scrfd_arcface_facerecognition_amd import lower
+    ref, _ = ep.cached_reference(key)
+    for name in names:
+        probe, low, (M, cin_p, cout_p, taps) = _split_geometry(key, name, monkeypatch)
+        f = tuple(int(v) for v in force.split(",")) if force else None
+        for cus in (64, 256, 304):
+            m = ep.split_mirror(M, cin_p, cout_p, taps, cus, f)
+            assert len(m["slabs"]) > 1 and sum(m["slabs"]) == m["ksteps"] and (slabs is None or m["slabs"] == slabs), (name, cus, m)
+        flags = int(low.ops[low.op_names.index(name)][11])
+        assert bool(flags & lower.CF_BORDER) == key.startswith("convbn") and bool(flags & lower.CF_RES_UP2) == key.startswith("up2")
+        n = next(x for x in probe.net.nodes if x.name == name)
+        first_of_last = sum(m["slabs"][:-1])
+        for fault, arg in (("fault_kstep", (m["bk"], cin_p, 0)), ("fault_kstep", (m["bk"], cin_p, first_of_last)),
+                           ("fault_kstep", (m["bk"], cin_p, m["ksteps"] - 1)), ("fault_bias_slabs", len(m["slabs"]))):
+            bad = ep.eval_node(n, ref, probe.P, fault, arg=arg)
+            with pytest.raises(AssertionError, match="values differ"):
+                ep.assert_same_bits(bad, ref[name], f"{key} / {name}")
+            assert (bad != ref[name]).any(axis=(1, 2, 3)).all(), (name, fault, arg)      # in every image
+    if key.startswith("conv-40x24"):                         # three 32-channel chunks per tap: some slab begins inside a tap
+        assert cin_p == 96 and any(sum(m["slabs"][:i]) % 3 for i in range(1, len(m["slabs"])))
+
+
+FC_KEYS = sorted(ep.FC_KEYS.values())
+
+
+@pytest.mark.parametrize("key", FC_KEYS)
+def test_fc_probe_faults_and_order(key):
+    """the FC reference does not depend on the order of the K-steps in fp32, and the comparator sees a dropped or doubled K-step of any slab, the
+    bias added once per slab and CHW-ordered weight columns"""
+    probe, ref, raw, _ = _probed(key)
+    n = probe.net.nodes[-1]
+    y = ref["fc"]
+    fwd, rev = ep.eval_fc(n, ref, probe.P, "f32_fwd"), ep.eval_fc(n, ref, probe.P, "f32_rev")
+    assert fwd.dtype == np.float32 and np.array_equal(fwd.view(np.uint32), rev.view(np.uint32)) and np.array_equal(fwd.astype(np.float64), y)
+    steps = n.h * n.w * ((n.c + 31) // 32 * 32) // ep.fc_bk(n)
+    faults = [("fault_kstep", s) for s in range(steps)] + [("fault_kstep_twice", 0), ("fault_kstep_twice", steps - 1), ("fault_bias_slabs", 3)]
+    if n.c % 32 == 0:
+        faults.append(("chw", None))
+    for fault, arg in faults:
+        bad = ep.eval_fc(n, ref, probe.P, fault, arg)
+        assert (bad != y).any(axis=1).all(), (key, fault, arg)              # in every image
+    with pytest.raises(AssertionError, match=r"values differ; first at \(0, \d+\)"):
+        ep.assert_same_values(ep.eval_fc(n, ref, probe.P, "fault_kstep", steps - 1).astype(np.float32), y.astype(np.float32), key)
+
+
+@pytest.mark.parametrize("key", FC_KEYS)
+def test_fc_probe_lowers_to_ideal_constants(key, monkeypatch):
+    """lower() with the BatchNorms as they stand and with the ideal affines: the same blob byte for byte; the FC is an OP_CONV with an fp32 result
+    on a flattened alias of its input, and the weight rows in the blob are fc_columns' (HWC order, zero columns for the padded channels)"""
+    from scrfd_arcface_facerecognition_amd import lower
+    probe, ref, raw, _ = _probed(key)
+    n = probe.net.nodes[-1]
+    real = lower.lower(probe.net, probe.P)
+    monkeypatch.setattr(lower, "_bn_affine", ep.ideal_affine)
+    ideal = lower.lower(probe.net, probe.P)
+    assert real.blob == ideal.blob and np.array_equal(real.ops, ideal.ops)
+    op = real.ops[real.op_names.index("fc")]
+    src, dst = real.tensors[int(op[1])], real.tensors[int(op[2])]
+    _, W, b = ep.fc_columns(n, ref, probe.P)
+    K = W.shape[1]
+    assert int(op[0]) == lower.OP_CONV and int(dst[4]) == 1 and (int(src[0]), int(src[1]), int(src[2]), int(src[3])) == (K, K, 1, 1)
+    got = np.frombuffer(real.blob, np.float16, count=int(op[17]) * K, offset=int(op[13])).reshape(int(op[17]), K)
+    assert np.array_equal(got[:n.cout].astype(np.float64), W) and not got[n.cout:].any()
+    assert np.array_equal(np.frombuffer(real.blob, np.float32, count=n.cout, offset=int(op[15])).astype(np.float64), b)
+    assert (ref["b"] < 0).any() and (ref["b"] > 0).any()
+
+
+@pytest.mark.parametrize("key", sorted(ep.STEMFUSED_KEYS.values()))
+def test_fused_stem_probe(key, monkeypatch):
+    """lowers to the one fused op (four ops with FID_NO_STEM_FUSE=1); a pooled row taken one row off at the seam of the 8-row and of the 6-row
+    tiles changes the reference, and so does a missing K-step of stem.2 (its power conditions: test_probe_conditions)"""
+    from scrfd_arcface_facerecognition_amd import lower
+    probe, ref, raw, held = _probed(key)
+    monkeypatch.delenv("FID_NO_STEM_FUSE", raising=False)
+    assert lower.lower(probe.net, probe.P).op_names == ["stem.fused"] and [n.name for n in held] == ["stem.2"]
+    monkeypatch.setenv("FID_NO_STEM_FUSE", "1")
+    assert [int(r[0]) for r in lower.lower(probe.net, probe.P).ops] == [lower.OP_STEM, lower.OP_CONV, lower.OP_CONV, lower.OP_MAXPOOL]
+    pool = probe.net.nodes[-1]
+    Hp, Wp = ref["stem.pool"].shape[1:3]
+    assert Hp % 8 != 0 or Hp % 6 != 0                        # ragged row tiles in one of the two forms at least
+    assert Wp % 6 != 0 or Hp == Wp == 16
+    for row in (6, 8):
+        bad = ep.eval_pool(pool, ref, "fault_row_off", row)
+        assert {int(i[1]) for i in np.argwhere(bad != ref["stem.pool"])} == {row}
+        with pytest.raises(AssertionError, match=rf"values differ; first \(n=0, y={row}, "):
+            ep.assert_same_bits(bad, ref["stem.pool"], key)
+
+
+@pytest.mark.parametrize("key", sorted(ep.FIRST_KEYS.values()))
+def test_first_conv_probe_lowers_to_the_stem_op(key):
+    from scrfd_arcface_facerecognition_amd import lower
+    probe = ep.PROBES[key]()
+    low = lower.lower(probe.net, probe.P)
+    n = probe.net.nodes[0]
+    assert [int(r[0]) for r in low.ops] == [lower.OP_STEM] and int(low.tensors[0][1]) == (n.cout + 31) // 32 * 32 and int(low.ops[0][6]) == n.stride
+
+
+@pytest.mark.parametrize("key", sorted(ep.POOL_KEYS.values()))
+def test_pool_probe_faults(key):
+    """zero padding and a pooled row taken one row off change the reference (the window and padding conditions: test_probe_conditions)"""
+    from scrfd_arcface_facerecognition_amd import lower
+    probe, ref, raw, _ = _probed(key)
+    pool = probe.net.nodes[-1]
+    low = lower.lower(probe.net, probe.P)
+    assert [int(r[0]) for r in low.ops] == [lower.OP_STEM, lower.OP_MAXPOOL]
+    H, W = ref["s"].shape[1:3]
+    Ho, Wo = ref["pool"].shape[1:3]
+    assert (Ho, Wo) == ((H - 1) // 2 + 1, (W - 1) // 2 + 1) and (ref["s"] < 0).mean() > 0.3
+    bad = ep.eval_pool(pool, ref, "fault_pad0")
+    with pytest.raises(AssertionError, match="values differ"):
+        ep.assert_same_bits(bad, ref["pool"], key)
+    rows = {int(i[1]) for i in np.argwhere(bad != ref["pool"])}
+    assert 0 in rows and (H % 2 == 0 or Ho - 1 in rows)      # the first row, and the last one where its window is clipped (odd maps)
+    assert (ep.eval_pool(pool, ref, "fault_row_off", Ho // 2) != ref["pool"]).any()
+
+
+@pytest.mark.parametrize("key", sorted(ep.GDC_KEYS.values()))
+def test_gdc_probe(key):
+    """lowers to a depthwise op that meets gdc_rows' dispatch condition; dense weights; every kernel row dropped changes every image"""
+    from scrfd_arcface_facerecognition_amd import lower
+    probe, ref, raw, held = _probed(key)
+    low = lower.lower(probe.net, probe.P)
+    assert ep.takes_gdc_rows(low, "g") and [n.name for n in held] == ["g"]
+    g = held[0]
+    assert (probe.P["g.weight"] != 0).all() and ref["g"].shape[1:3] == (1, 1)
+    for row in range(g.k):
+        bad = ep.eval_node(g, ref, probe.P, "fault_row", arg=row)
+        assert (bad != ref["g"]).any(axis=(1, 2, 3)).all(), (key, row)
+    with pytest.raises(AssertionError, match="values differ"):
+        ep.assert_same_bits(ep.eval_node(g, ref, probe.P, "fault_row", arg=g.k - 1), ref["g"], key)
