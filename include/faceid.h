@@ -141,6 +141,23 @@ int fid_letterbox(fid_ctx *ctx, const uint8_t *frames_dev, int B, int H, int W,
 int fid_letterbox_ragged(fid_ctx *ctx, const uint8_t *frames_dev, size_t frames_bytes, const int32_t *hw, const int64_t *offsets,
                          int B, uint8_t *out_dev, int in_h, int in_w, double *det_scale);
 
+/* ---- tiled detection: frames larger than the detector input, seen at the resolution they were filmed in.  (No reference analogue:
+ * models/scrfd.py:123-138 letterboxes the whole frame, so a 1080p frame reaches a 640x640 detector at one third of its scale.)
+ * A tile table is a HOST int32 [T,6] array, one row per tile: frame, x0, y0, w, h, kind.
+ *   kind 0  native: the rectangle (x0, y0, w, h) of frame `frame` is copied 1:1 to the top-left of the detector input, the rest of the
+ *           input is zero; w <= in_w, h <= in_h; its det_scale is exactly 1.0f.
+ *   kind 1  letterboxed: the rectangle is resized into the input with the geometry and pixel arithmetic fid_letterbox uses for an h x w
+ *           image; det_scale = (float)(new_h / (double)h).  A kind 1 row that covers a whole frame is byte for byte fid_letterbox of it.
+ * Rows of one frame are contiguous and frames appear in ascending order; the position of a row within its frame is its tile rank.
+ * Validation is all-or-nothing: a frame outside [0, B), a rectangle not inside the frame, w or h <= 0, a kind 0 tile larger than the input,
+ * a degenerate letterbox, rows not grouped by ascending frame or an unknown kind return FID_E_INVALID with the row index in
+ * fid_last_error(), and nothing is enqueued.  The table travels to a device table the context owns, ordered on the context's stream: it
+ * may be freed or overwritten as soon as a call returns, and no call synchronises with the host.  T <= 65535.
+ *
+ * fid_tile_cut: frames [B,H,W,3] -> out [T,in_h,in_w,3], one launch for all tiles; no byte outside frames is read. */
+int fid_tile_cut(fid_ctx *ctx, const uint8_t *frames_dev, int B, int H, int W, const int32_t *tiles, int T,
+                 uint8_t *out_dev, int in_h, int in_w);
+
 /* ---- SCRFD post-process: replaces the numpy code of reference models/scrfd.py:89-178,180-207
  * and utils/helpers.py:62-107 (threshold, distance2bbox/kps decode, sort, greedy NMS, max_num).
  * The 9 head tensors (scores, bbox, kps for strides 8/16/32) are given as strided views so both
@@ -164,6 +181,21 @@ int fid_scrfd_postprocess_ragged(fid_ctx *ctx, const float *const head_dev[9], c
                                  const int32_t anc_stride[9], const int64_t batch_stride[9], int B, int in_h, int in_w,
                                  int num_anchors, const int32_t *hw, float conf_thres, float iou_thres, int max_num, int metric,
                                  float *det_dev, float *kps_dev, int32_t *counts_dev, int cap);
+/* The same for tiled detection: the head tensors have batch dimension T (the detector's run over fid_tile_cut's output), the outputs
+ * batch dimension B, in fid_scrfd_postprocess's layout; tiles is the table fid_tile_cut took, the frames are img_h x img_w.  Tile t decodes
+ * as a frame of fid_scrfd_postprocess does with its own det_scale; every coordinate v then becomes (v / det_scale) + (float)x0 (y0 for y
+ * values), two single rounded fp32 operations, and the candidate joins the list of the tile's frame.  Inside a frame equal scores fall in
+ * (tile rank, anchor) order; tiles per frame x anchors must stay below 2^31.
+ * Edge rule (m = edge_margin; m < 0 switches it off), on the frame-coordinate box in fp32: a candidate is dropped before it takes a slot if
+ *   x0 > 0 && x1 < x0 + m,   y0 > 0 && y1 < y0 + m,   x0 + w < img_w && x2 > x0 + w - m   or   y0 + h < img_h && y2 > y0 + h - m
+ * -- the half faces a tile sees at a cut; a side that lies on the frame's boundary never rejects.
+ * Sort, NMS (one per frame, over the candidates of all its tiles), max_num around the FRAME's centre and the capacity report through
+ * fid_scrfd_check are those of fid_scrfd_postprocess: cand_cap bounds the candidates of a frame's tiles together.  A table of one kind 1 row
+ * per frame that covers it gives fid_scrfd_postprocess's det, kps and counts. */
+int fid_scrfd_postprocess_tiled(fid_ctx *ctx, const float *const head_dev[9], const int32_t pix_stride[9],
+                                const int32_t anc_stride[9], const int64_t batch_stride[9], const int32_t *tiles, int T,
+                                int in_h, int in_w, int num_anchors, int B, int img_h, int img_w, float conf_thres, float iou_thres,
+                                int edge_margin, int max_num, int metric, float *det_dev, float *kps_dev, int32_t *counts_dev, int cap);
 /* candidates per frame the sort/NMS workspace is sized for (default 4096; max 16800 = all anchors
  * of a 640x640 input) */
 int fid_scrfd_set_candidate_capacity(fid_ctx *ctx, int cand_cap);

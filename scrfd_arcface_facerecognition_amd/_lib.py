@@ -116,6 +116,10 @@ SIGNATURES = {
                                          C.c_void_p, C.c_void_p]),
     "fid_align_crops_packed_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, c_i32_p, c_i64_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.c_void_p]),
+    "fid_tile_cut": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_i32_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    "fid_scrfd_postprocess_tiled": (C.c_int, [C.c_void_p, c_void_pp, c_i32_p, c_i32_p, c_i64_p, c_i32_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_int]),
     "fid_scrfd_postprocess": (C.c_int, [C.c_void_p, c_void_pp, c_i32_p, c_i32_p, c_i64_p, C.c_int, C.c_int,
                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),

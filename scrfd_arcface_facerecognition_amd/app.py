@@ -64,14 +64,23 @@ class FaceAnalysis:
         self.last_verdict = None                              # of the last best_face(): one of VERDICTS
         self.last_batch_best = []                             # of the last get_batch(): per image (best face index, FID_GATE_* verdict)
 
-    def prepare(self, ctx_id: int = 0, det_size=(640, 640), det_thresh: Optional[float] = None):
-        """insightface API compatibility (smart_face_recognition.py:358)"""
+    tiled, tile_overlap, tile_margin = False, 128, 8         # prepare(tiled=True, ...) changes them
+
+    def prepare(self, ctx_id: int = 0, det_size=(640, 640), det_thresh: Optional[float] = None, tiled: bool = False, tile_overlap: int = 128,
+                tile_margin: int = 8):
+        """insightface API compatibility (smart_face_recognition.py:358).  tiled=True: get / get_batch on images of one size detect tiled
+        (SCRFD.detect_tiled: native-resolution tiles `tile_overlap` pixels apart plus one overview tile, candidates within `tile_margin`
+        pixels of a cut dropped); a get_batch list whose images differ in size keeps the mixed-size path, which letterboxes every image whole."""
         self.det.input_size = det_size
         if det_thresh is not None:
             self.det.conf_thres = det_thresh
+        self.tiled, self.tile_overlap, self.tile_margin = bool(tiled), int(tile_overlap), int(tile_margin)
 
     def get(self, image: np.ndarray, max_num: int = 0) -> List[Face]:
-        det, kpss = self.det.detect(image, max_num=max_num)
+        if self.tiled:
+            det, kpss = self.det.detect_tiled(image, max_num=max_num, overlap=self.tile_overlap, edge_margin=self.tile_margin)
+        else:
+            det, kpss = self.det.detect(image, max_num=max_num)
         n = min(len(det), self.max_faces)
         if n == 0:
             return []
@@ -116,12 +125,14 @@ class FaceAnalysis:
         net = self.rec.session.compiled()
         out: List[List[Face]] = []
         bests: List[tuple] = []                               # per image (best face index or -1, FID_GATE_* verdict): process_visits reads it
-        step = self.det._max_batch
+        tiled = self.tiled and not mixed                      # (a mixed-size list keeps the ragged path: prepare's docstring)
+        step = self.det.tiled_frames_per_chunk(H, W, self.tile_overlap) if tiled else self.det._max_batch
         for b0 in range(0, len(images), step):
             chunk = images[b0:b0 + step]
             B = len(chunk)
             batch = ctx.image_batch(chunk) if mixed else None
             dets = (self.det._detect_chunk_ragged(chunk, max_num, "max", batch) if mixed
+                    else self.det._detect_chunk_tiled(chunk, max_num, "max", self.tile_overlap, self.tile_margin) if tiled
                     else self.det._detect_chunk(chunk, max_num, "max"))   # host results; the post-process's device arrays stay valid
             post = self.det._postprocessor()
             total = sum(len(d) for d, _ in dets)

@@ -138,19 +138,20 @@ __global__ void __launch_bounds__(256) align_warp_packed_ragged(const uint8_t *f
 }
 
 // cv2.resize INTER_LINEAR u8 + zero letterbox paste (scrfd.py:135-138): output pixel (x, y) of one image, written to o.
-// Shared by the uniform and the mixed-size kernels: the two write the same bytes by construction.
-__device__ __forceinline__ void letterbox_pixel(const uint8_t *src, int H, int W, uint8_t *o, int x, int y, int new_h, int new_w,
+// Shared by the uniform, the mixed-size and the tile kernels: they write the same bytes by construction.  `ld` = pixels from one source row
+// to the next: W for a dense image, the frame's width for a rectangle of a frame (fid_tile_cut).
+__device__ __forceinline__ void letterbox_pixel(const uint8_t *src, int H, int W, int ld, uint8_t *o, int x, int y, int new_h, int new_w,
                                                 double scale_x, double scale_y, int area2x) {
     if (x >= new_w || y >= new_h) { o[0] = o[1] = o[2] = 0; return; }
     if (new_w == W && new_h == H) {
-        const uint8_t *q = src + ((size_t)y * W + x) * 3;
+        const uint8_t *q = src + ((size_t)y * ld + x) * 3;
         o[0] = q[0]; o[1] = q[1]; o[2] = q[2];
         return;
     }
     if (area2x) {  // exact 2x decimation is INTER_AREA inside cv2.resize
         for (int c = 0; c < 3; c++) {
-            const int s = src[((size_t)(2 * y) * W + 2 * x) * 3 + c] + src[((size_t)(2 * y) * W + 2 * x + 1) * 3 + c] +
-                          src[((size_t)(2 * y + 1) * W + 2 * x) * 3 + c] + src[((size_t)(2 * y + 1) * W + 2 * x + 1) * 3 + c];
+            const int s = src[((size_t)(2 * y) * ld + 2 * x) * 3 + c] + src[((size_t)(2 * y) * ld + 2 * x + 1) * 3 + c] +
+                          src[((size_t)(2 * y + 1) * ld + 2 * x) * 3 + c] + src[((size_t)(2 * y + 1) * ld + 2 * x + 1) * 3 + c];
             o[c] = (uint8_t)((s + 2) >> 2);
         }
         return;
@@ -169,8 +170,8 @@ __device__ __forceinline__ void letterbox_pixel(const uint8_t *src, int H, int W
     coeff(x, scale_x, W, sx0, sx1, a0, a1);
     coeff(y, scale_y, H, sy0, sy1, b0, b1);
     for (int c = 0; c < 3; c++) {
-        const int T0 = src[((size_t)sy0 * W + sx0) * 3 + c] * a0 + src[((size_t)sy0 * W + sx1) * 3 + c] * a1;
-        const int T1 = src[((size_t)sy1 * W + sx0) * 3 + c] * a0 + src[((size_t)sy1 * W + sx1) * 3 + c] * a1;
+        const int T0 = src[((size_t)sy0 * ld + sx0) * 3 + c] * a0 + src[((size_t)sy0 * ld + sx1) * 3 + c] * a1;
+        const int T1 = src[((size_t)sy1 * ld + sx0) * 3 + c] * a0 + src[((size_t)sy1 * ld + sx1) * 3 + c] * a1;
         int v = (((b0 * (T0 >> 4)) >> 16) + ((b1 * (T1 >> 4)) >> 16) + 2) >> 2;
         o[c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
     }
@@ -181,7 +182,7 @@ __global__ void __launch_bounds__(256) letterbox_kernel(const uint8_t *frames, i
     const int b = blockIdx.z;
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= in_w) return;
-    letterbox_pixel(frames + (size_t)b * H * W * 3, H, W, out + (((size_t)b * in_h + y) * in_w + x) * 3, x, y, new_h, new_w, scale_x, scale_y,
+    letterbox_pixel(frames + (size_t)b * H * W * 3, H, W, W, out + (((size_t)b * in_h + y) * in_w + x) * 3, x, y, new_h, new_w, scale_x, scale_y,
                     area2x);
 }
 
@@ -191,7 +192,7 @@ __global__ void __launch_bounds__(256) letterbox_kernel_ragged(const uint8_t *fr
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= in_w) return;
     const fid::RaggedImg g = tab[b];
-    letterbox_pixel(frames + g.off, g.H, g.W, out + (((size_t)b * in_h + y) * in_w + x) * 3, x, y, g.new_h, g.new_w, g.scale_x, g.scale_y,
+    letterbox_pixel(frames + g.off, g.H, g.W, g.W, out + (((size_t)b * in_h + y) * in_w + x) * 3, x, y, g.new_h, g.new_w, g.scale_x, g.scale_y,
                     g.mode == 2);
 }
 
@@ -199,8 +200,8 @@ __global__ void __launch_bounds__(256) letterbox_kernel_ragged(const uint8_t *fr
 // 1-byte loads and the 12 output bytes leave as three aligned dwords -- 16 + 3 memory instructions per 4 pixels instead of 48 + 12 (32 frames of
 // 1080p -> 640x640: cfg 5 step 1.548 -> 1.535 ms).  `src_bytes` = bytes of the whole frame batch: the last pixel of the batch is read bytewise.
 // Shared by the uniform and the mixed-size kernel, like letterbox_pixel.
-// letterbox_pixels4: output pixels x4 .. x4+3 of row y of the image whose first byte is frames[fbase], as three dwords at o.
-__device__ __forceinline__ void letterbox_pixels4(const uint8_t *frames, size_t fbase, int H, int W, unsigned *o, int x4, int y, int new_h, int new_w,
+// letterbox_pixels4: output pixels x4 .. x4+3 of row y of the image whose first byte is frames[fbase] (rows `ld` pixels apart), as three dwords at o.
+__device__ __forceinline__ void letterbox_pixels4(const uint8_t *frames, size_t fbase, int H, int W, int ld, unsigned *o, int x4, int y, int new_h, int new_w,
                                                   double scale_x, double scale_y, size_t src_bytes) {
     unsigned char px[12];
     auto fetch = [&](size_t off) -> unsigned {                  // the 3 bytes of a source pixel (byte 3 of the word is ignored)
@@ -229,8 +230,8 @@ __device__ __forceinline__ void letterbox_pixels4(const uint8_t *frames, size_t 
         if (x >= new_w || y >= new_h) { px[3 * i] = px[3 * i + 1] = px[3 * i + 2] = 0; continue; }
         int sx0, sx1, a0, a1;
         coeff(x, scale_x, W, sx0, sx1, a0, a1);
-        const unsigned p00 = fetch(fbase + ((size_t)sy0 * W + sx0) * 3), p01 = fetch(fbase + ((size_t)sy0 * W + sx1) * 3);
-        const unsigned p10 = fetch(fbase + ((size_t)sy1 * W + sx0) * 3), p11 = fetch(fbase + ((size_t)sy1 * W + sx1) * 3);
+        const unsigned p00 = fetch(fbase + ((size_t)sy0 * ld + sx0) * 3), p01 = fetch(fbase + ((size_t)sy0 * ld + sx1) * 3);
+        const unsigned p10 = fetch(fbase + ((size_t)sy1 * ld + sx0) * 3), p11 = fetch(fbase + ((size_t)sy1 * ld + sx1) * 3);
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             const int T0 = (int)((p00 >> (8 * c)) & 255u) * a0 + (int)((p01 >> (8 * c)) & 255u) * a1;
@@ -249,7 +250,7 @@ __global__ void __launch_bounds__(256) letterbox_kernel4(const uint8_t *frames, 
     const int b = blockIdx.z;
     const int x4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, y = blockIdx.y;
     if (x4 >= in_w) return;
-    letterbox_pixels4(frames, (size_t)b * H * W * 3, H, W, (unsigned *)(out + (((size_t)b * in_h + y) * in_w + x4) * 3), x4, y, new_h, new_w,
+    letterbox_pixels4(frames, (size_t)b * H * W * 3, H, W, W, (unsigned *)(out + (((size_t)b * in_h + y) * in_w + x4) * 3), x4, y, new_h, new_w,
                       scale_x, scale_y, src_bytes);
 }
 
@@ -264,10 +265,56 @@ __global__ void __launch_bounds__(256) letterbox_kernel4_ragged(const uint8_t *f
     uint8_t *o = out + (((size_t)b * in_h + y) * in_w + x4) * 3;
     if (g.mode != 0) {
         for (int i = 0; i < 4; i++)
-            letterbox_pixel(frames + g.off, g.H, g.W, o + 3 * i, x4 + i, y, g.new_h, g.new_w, g.scale_x, g.scale_y, g.mode == 2);
+            letterbox_pixel(frames + g.off, g.H, g.W, g.W, o + 3 * i, x4 + i, y, g.new_h, g.new_w, g.scale_x, g.scale_y, g.mode == 2);
         return;
     }
-    letterbox_pixels4(frames, (size_t)g.off, g.H, g.W, (unsigned *)o, x4, y, g.new_h, g.new_w, g.scale_x, g.scale_y, src_bytes);
+    letterbox_pixels4(frames, (size_t)g.off, g.H, g.W, g.W, (unsigned *)o, x4, y, g.new_h, g.new_w, g.scale_x, g.scale_y, src_bytes);
+}
+
+// ---- tiled detection (fid_tile_cut): tile blockIdx.z of the table is cut from its frame into its own detector input ----
+// A native tile (kind 0) is the rectangle copied to the top-left corner, the rest zero; a letterboxed one (kind 1) is letterbox_pixel /
+// letterbox_pixels4 on the rectangle, whose rows are W pixels apart.  Only bytes of pixels inside the rectangle are read, except the
+// guarded 4-byte fetch of letterbox_pixels4, which stays inside the frame batch.
+__global__ void __launch_bounds__(256) tile_cut_kernel(const uint8_t *frames, int H, int W, const fid::TileEntry *tab, uint8_t *out, int in_h, int in_w) {
+    const int t = blockIdx.z;
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= in_w) return;
+    const fid::TileEntry g = tab[t];
+    const uint8_t *src = frames + (((size_t)g.frame * H + g.y0) * W + g.x0) * 3;
+    // (kind 0: new_h x new_w == h x w, which letterbox_pixel copies 1:1 and pads with zeros)
+    letterbox_pixel(src, g.h, g.w, W, out + (((size_t)t * in_h + y) * in_w + x) * 3, x, y, g.new_h, g.new_w, g.scale_x, g.scale_y, g.mode == 2);
+}
+
+// four output pixels per thread as three aligned dwords (in_w % 4 == 0), like letterbox_kernel4.  The branches are block-uniform.
+__global__ void __launch_bounds__(256) tile_cut_kernel4(const uint8_t *frames, int H, int W, const fid::TileEntry *tab, uint8_t *out, int in_h, int in_w,
+                                                        size_t src_bytes) {
+    const int t = blockIdx.z;
+    const int x4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, y = blockIdx.y;
+    if (x4 >= in_w) return;
+    const fid::TileEntry g = tab[t];
+    const size_t fbase = (((size_t)g.frame * H + g.y0) * W + g.x0) * 3;
+    uint8_t *o = out + (((size_t)t * in_h + y) * in_w + x4) * 3;
+    if (g.kind == 0) {
+        unsigned v[3] = {0u, 0u, 0u};
+        if (y < g.h && x4 < g.w) {
+            const uint8_t *q = frames + fbase + ((size_t)y * W + x4) * 3;     // (unaligned when W is odd or x0 is no multiple of 4)
+            if (x4 + 4 <= g.w) {
+                __builtin_memcpy(v, q, 12);                                    // the 12 bytes of four pixels inside the rectangle
+            } else {
+                const int nb = (g.w - x4) * 3;                                 // 3, 6 or 9 bytes: the row's last pixels, then zeros
+                for (int k = 0; k < nb; k++) v[k >> 2] |= (unsigned)q[k] << (8 * (k & 3));
+            }
+        }
+        unsigned *ow = (unsigned *)o;
+        ow[0] = v[0]; ow[1] = v[1]; ow[2] = v[2];
+        return;
+    }
+    if (g.mode != 0) {
+        for (int i = 0; i < 4; i++)
+            letterbox_pixel(frames + fbase, g.h, g.w, W, o + 3 * i, x4 + i, y, g.new_h, g.new_w, g.scale_x, g.scale_y, g.mode == 2);
+        return;
+    }
+    letterbox_pixels4(frames, fbase, g.h, g.w, W, (unsigned *)o, x4, y, g.new_h, g.new_w, g.scale_x, g.scale_y, src_bytes);
 }
 
 // Host half of the mixed-size entry points: validate every image and compute its table entry (all-or-nothing: the caller enqueues nothing
@@ -347,6 +394,27 @@ int fid_letterbox(fid_ctx *ctx, const uint8_t *frames_dev, int B, int H, int W, 
     }
     hipLaunchKernelGGL(letterbox_kernel, grid, dim3(256), 0, ctx->stream, frames_dev, H, W, out_dev, in_h, in_w, new_h, new_w,
                        (double)W / (double)new_w, (double)H / (double)new_h, area2x);
+    FID_HIP(hipGetLastError());
+    return FID_OK;
+}
+
+// ---- tiled detection: T rectangles of the frames, each cut into its own detector input (tiles: host [T,6], include/faceid.h) ----
+int fid_tile_cut(fid_ctx *ctx, const uint8_t *frames_dev, int B, int H, int W, const int32_t *tiles, int T, uint8_t *out_dev, int in_h, int in_w) {
+    FID_REQUIRE(ctx && frames_dev && tiles && out_dev, "NULL argument");
+    FID_REQUIRE(B > 0 && H > 0 && W > 0 && in_h > 0 && in_w > 0 && T > 0 && T <= 65535 && in_h <= 65535, "bad sizes");
+    std::vector<fid::TileEntry> host;
+    FID_TRY(fid::tile_entries(tiles, T, B, H, W, in_h, in_w, host, nullptr));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
+    const fid::TileEntry *tab;
+    FID_TRY(fid::tile_table(ctx, host.data(), T, &tab));
+    if (in_w % 4 == 0 && ((size_t)out_dev & 3) == 0) {
+        dim3 grid4(fid::cdiv(in_w / 4, 256), in_h, T);
+        hipLaunchKernelGGL(tile_cut_kernel4, grid4, dim3(256), 0, ctx->stream, frames_dev, H, W, tab, out_dev, in_h, in_w, (size_t)B * H * W * 3);
+    } else {
+        dim3 grid(fid::cdiv(in_w, 256), in_h, T);
+        hipLaunchKernelGGL(tile_cut_kernel, grid, dim3(256), 0, ctx->stream, frames_dev, H, W, tab, out_dev, in_h, in_w);
+    }
     FID_HIP(hipGetLastError());
     return FID_OK;
 }

@@ -95,6 +95,9 @@ struct fid_ctx {
     // per-image geometry table of the *_ragged entry points (fid::ragged_table): grows, never shrinks
     void *ragged_tab = nullptr;
     int ragged_tab_cap = 0;         // entries
+    // tile table of the tiled detection entry points (fid::tile_table): grows, never shrinks
+    void *tile_tab = nullptr;
+    int tile_tab_cap = 0;           // entries
 };
 
 namespace fid {
@@ -135,4 +138,23 @@ inline bool ragged_geometry(int H, int W, int in_h, int in_w, RaggedImg *g) {
 // small store kernels, so the host array is free when this returns, the write runs after every earlier reader of the table, and
 // nothing synchronises with the host (the table only reallocates, behind a stream synchronise, when B outgrows it).
 int ragged_table(fid_ctx *ctx, const RaggedImg *host, int B, const RaggedImg **dev);
+
+// One tile of a tiled detection (fid_tile_cut / fid_scrfd_postprocess_tiled): a row of the caller's [T,6] table plus what the host derives
+// from it.  kind 0 (native): the rectangle is copied 1:1, det_scale is exactly 1.0f.  kind 1 (letterboxed): the rectangle is resized with
+// the geometry ragged_geometry computes for an h x w image.  Every stage reads the entry of its tile by a block-uniform index.
+struct TileEntry {
+    int frame, x0, y0, w, h, kind;
+    int new_h, new_w;           // resized size inside the detector input (kind 0: h, w)
+    double scale_x, scale_y;    // w / new_w, h / new_h
+    float det_scale;            // what the post-process divides by
+    int mode;                   // kind 1: RaggedImg::mode of the rectangle
+    int rank;                   // position of the tile among its frame's tiles
+    int pad_;
+};
+static_assert(sizeof(TileEntry) == 64, "TileEntry is copied to the device as 64-byte entries");
+// Validate a host [T,6] table (frame, x0, y0, w, h, kind) against B frames of H x W and the detector input and fill the entries: all or
+// nothing, FID_E_INVALID names the first bad row in fid_last_error().  max_per_frame: the largest number of tiles one frame has (may be NULL).
+int tile_entries(const int32_t *tiles, int T, int B, int H, int W, int in_h, int in_w, std::vector<TileEntry> &tab, int *max_per_frame);
+// ragged_table for tile entries: the same ordering and lifetime guarantees
+int tile_table(fid_ctx *ctx, const TileEntry *host, int T, const TileEntry **dev);
 }  // namespace fid

@@ -86,6 +86,67 @@ int ragged_table(fid_ctx *ctx, const RaggedImg *host, int B, const RaggedImg **d
     *dev = tab;
     return FID_OK;
 }
+// ---- the tile table of the tiled detection entry points ----
+int tile_entries(const int32_t *tiles, int T, int B, int H, int W, int in_h, int in_w, std::vector<TileEntry> &tab, int *max_per_frame) {
+    tab.resize(T);
+    int rank = 0, most = 0;
+    for (int t = 0; t < T; t++) {
+        const int32_t *r = tiles + 6 * (size_t)t;
+        TileEntry e{};
+        e.frame = r[0]; e.x0 = r[1]; e.y0 = r[2]; e.w = r[3]; e.h = r[4]; e.kind = r[5];
+        FID_REQUIRE(e.frame >= 0 && e.frame < B, "tile %d: frame %d outside [0, %d)", t, e.frame, B);
+        FID_REQUIRE(t == 0 || e.frame >= tab[t - 1].frame, "tile %d: frame %d after frame %d (rows must be grouped by ascending frame)", t, e.frame,
+                    t ? tab[t - 1].frame : 0);
+        FID_REQUIRE(e.w > 0 && e.h > 0, "tile %d: bad size %dx%d", t, e.w, e.h);
+        FID_REQUIRE(e.x0 >= 0 && e.y0 >= 0 && (long long)e.x0 + e.w <= W && (long long)e.y0 + e.h <= H,
+                    "tile %d: rectangle (%d, %d) %dx%d leaves the %dx%d frame", t, e.x0, e.y0, e.w, e.h, W, H);
+        if (e.kind == 0) {
+            FID_REQUIRE(e.w <= in_w && e.h <= in_h, "tile %d: native tile %dx%d larger than the %dx%d input", t, e.w, e.h, in_w, in_h);
+            e.new_h = e.h; e.new_w = e.w; e.scale_x = e.scale_y = 1.0; e.det_scale = 1.0f; e.mode = 1;
+        } else if (e.kind == 1) {
+            RaggedImg g{};
+            FID_REQUIRE(ragged_geometry(e.h, e.w, in_h, in_w, &g), "tile %d: degenerate letterbox %dx%d", t, g.new_w, g.new_h);
+            e.new_h = g.new_h; e.new_w = g.new_w; e.scale_x = g.scale_x; e.scale_y = g.scale_y; e.det_scale = g.det_scale; e.mode = g.mode;
+        } else {
+            FID_REQUIRE(false, "tile %d: unknown kind %d", t, e.kind);
+        }
+        rank = (t > 0 && e.frame == tab[t - 1].frame) ? rank + 1 : 0;
+        e.rank = rank;
+        most = std::max(most, rank + 1);
+        tab[t] = e;
+    }
+    if (max_per_frame) *max_per_frame = most;
+    return FID_OK;
+}
+constexpr int TILE_CHUNK = 48;                // entries per store kernel: 48 x 64 B = 3 KB of the 4 KB a kernel's arguments may take
+struct TileChunk { TileEntry e[TILE_CHUNK]; };
+__global__ void __launch_bounds__(64) tile_table_store(TileChunk c, int n, TileEntry *dst) {
+    if ((int)threadIdx.x < n) dst[threadIdx.x] = c.e[threadIdx.x];
+}
+int tile_table(fid_ctx *ctx, const TileEntry *host, int T, const TileEntry **dev) {
+    if (ctx->tile_tab_cap < T) {
+        if (ctx->tile_tab) {
+            FID_HIP(hipStreamSynchronize(ctx->stream));
+            FID_HIP(hipFree(ctx->tile_tab));
+            ctx->tile_tab = nullptr;
+            ctx->tile_tab_cap = 0;
+        }
+        const int want = std::max(1024, T + T / 4);
+        FID_HIP(hipMalloc(&ctx->tile_tab, (size_t)want * sizeof(TileEntry)));
+        ctx->tile_tab_cap = want;
+    }
+    TileEntry *tab = (TileEntry *)ctx->tile_tab;
+    TileChunk c;
+    for (int t0 = 0; t0 < T; t0 += TILE_CHUNK) {
+        const int n = std::min(TILE_CHUNK, T - t0);
+        memcpy(c.e, host + t0, (size_t)n * sizeof(TileEntry));
+        if (n < TILE_CHUNK) memset(c.e + n, 0, (size_t)(TILE_CHUNK - n) * sizeof(TileEntry));
+        hipLaunchKernelGGL(tile_table_store, dim3(1), dim3(64), 0, ctx->stream, c, n, tab + t0);
+    }
+    FID_HIP(hipGetLastError());
+    *dev = tab;
+    return FID_OK;
+}
 }  // namespace fid
 
 extern "C" {
@@ -135,6 +196,7 @@ int fid_ctx_destroy(fid_ctx *ctx) {
         if (ctx->events[i]) (void)hipEventDestroy(ctx->events[i]);
     if (ctx->status_dev) (void)hipFree(ctx->status_dev);
     if (ctx->ragged_tab) (void)hipFree(ctx->ragged_tab);
+    if (ctx->tile_tab) (void)hipFree(ctx->tile_tab);
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
     if (ctx->copy_done) (void)hipEventDestroy(ctx->copy_done);
     if (ctx->compute_done) (void)hipEventDestroy(ctx->compute_done);

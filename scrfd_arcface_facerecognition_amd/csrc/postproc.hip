@@ -81,6 +81,58 @@ __global__ void __launch_bounds__(256) decode_compact_ragged(HeadViews hv, int i
     decode_compact_frame(hv, blockIdx.y, in_h, in_w, A, thr, tab[blockIdx.y].det_scale, 0, cand_cap, cand_count, cand_key, cand_data);
 }
 
+// Tiled detection: head batch entry blockIdx.y is tile t of the table, its candidates join frame tab[t].frame's list in FRAME coordinates.
+// The decode is decode_compact_frame's, operation for operation; every coordinate then moves by the tile's origin,
+// (v / det_scale) + (float)x0 or y0, two single rounded fp32 operations.  A candidate whose frame box comes within `margin` pixels of a side
+// of the tile that is a cut (not the frame's boundary) is dropped before it takes a slot: the half face a tile sees at a cut (margin < 0: no
+// rule).  Order inside a frame: score descending, then (tile rank, anchor) ascending -- what concatenating the tiles' candidate arrays in table
+// order and the oracle's two stable sorts produce.
+__global__ void __launch_bounds__(256) decode_compact_tiled(HeadViews hv, int in_h, int in_w, int A, float thr, const fid::TileEntry *tab,
+                                                            int img_h, int img_w, int margin, int cand_cap, int *cand_count,
+                                                            unsigned long long *cand_key, float *cand_data) {
+    const int n8 = (in_h / 8) * (in_w / 8) * A, n16 = (in_h / 16) * (in_w / 16) * A, n32 = (in_h / 32) * (in_w / 32) * A;
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;  // flat anchor index over the 3 levels
+    if (g >= n8 + n16 + n32) return;
+    const int t = blockIdx.y;
+    const fid::TileEntry e = tab[t];
+    int lvl, i, stride;
+    if (g < n8) { lvl = 0; i = g; stride = 8; }
+    else if (g < n8 + n16) { lvl = 1; i = g - n8; stride = 16; }
+    else { lvl = 2; i = g - n8 - n16; stride = 32; }
+    const int pix = i / A, a = i - pix * A;
+    const float score = hv.ptr[lvl][t * hv.batch_stride[lvl] + (long long)pix * hv.pix_stride[lvl] + a * hv.anc_stride[lvl]];
+    if (!(score >= thr)) return;
+    const int fw = in_w / stride;
+    const float cx = (float)((pix % fw) * stride), cy = (float)((pix / fw) * stride);
+    const float fs = (float)stride, ds = e.det_scale, ox = (float)e.x0, oy = (float)e.y0;
+    const float *bp = hv.ptr[3 + lvl] + t * hv.batch_stride[3 + lvl] + (long long)pix * hv.pix_stride[3 + lvl] + a * hv.anc_stride[3 + lvl];
+    const float X1 = __fadd_rn(__fdiv_rn(__fsub_rn(cx, __fmul_rn(bp[0], fs)), ds), ox);
+    const float Y1 = __fadd_rn(__fdiv_rn(__fsub_rn(cy, __fmul_rn(bp[1], fs)), ds), oy);
+    const float X2 = __fadd_rn(__fdiv_rn(__fadd_rn(cx, __fmul_rn(bp[2], fs)), ds), ox);
+    const float Y2 = __fadd_rn(__fdiv_rn(__fadd_rn(cy, __fmul_rn(bp[3], fs)), ds), oy);
+    if (margin >= 0) {
+        if (e.x0 > 0 && X1 < (float)(e.x0 + margin)) return;
+        if (e.y0 > 0 && Y1 < (float)(e.y0 + margin)) return;
+        if (e.x0 + e.w < img_w && X2 > (float)(e.x0 + e.w - margin)) return;
+        if (e.y0 + e.h < img_h && Y2 > (float)(e.y0 + e.h - margin)) return;
+    }
+    const int b = e.frame;
+    const int slot = atomicAdd(&cand_count[b], 1);
+    if (slot >= cand_cap) return;  // overflow is reported through the count itself
+    const float *kp = hv.ptr[6 + lvl] + t * hv.batch_stride[6 + lvl] + (long long)pix * hv.pix_stride[6 + lvl] + a * hv.anc_stride[6 + lvl];
+    float *o = cand_data + ((size_t)b * cand_cap + slot) * CAND_W;
+    o[0] = X1; o[1] = Y1; o[2] = X2; o[3] = Y2;
+    o[4] = score;
+#pragma unroll
+    for (int k = 0; k < 5; k++) {
+        o[5 + 2 * k] = __fadd_rn(__fdiv_rn(__fadd_rn(cx, __fmul_rn(kp[2 * k], fs)), ds), ox);
+        o[6 + 2 * k] = __fadd_rn(__fdiv_rn(__fadd_rn(cy, __fmul_rn(kp[2 * k + 1], fs)), ds), oy);
+    }
+    const unsigned idx = (unsigned)e.rank * (unsigned)(n8 + n16 + n32) + (unsigned)g;   // < 2^31: checked by the launcher
+    o[15] = __int_as_float((int)idx);
+    cand_key[(size_t)b * cand_cap + slot] = ((unsigned long long)sortable(score) << 32) | (unsigned)(~idx);
+}
+
 // distance2bbox / distance2kps on plain arrays (utils/helpers.py:62-107): ncol = 4 -> bbox, else kps pairs
 __global__ void decode_points(const float *points, const float *dist, int n, int ncol, float *out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -303,9 +355,11 @@ static size_t nms_lds_bytes(int cand_cap, int *n_box) {
 }
 // shared by fid_scrfd_postprocess and the fused pipeline
 // tab != NULL: a mixed-size batch -- det_scale and the image size of frame b come from tab[b], img_h / img_w are unused
+// tiles != NULL: tiled detection -- the heads hold T tiles, whose candidates join the lists of the B frames they were cut from (decode_compact_tiled)
 int scrfd_postprocess_launch(fid_ctx *ctx, const HeadViews &hv, int B, int in_h, int in_w, int A, int img_h, int img_w,
                              float conf, float iou, int max_num, int metric, float *det_dev, float *kps_dev,
-                             int32_t *counts_dev, int cap, const RaggedImg *tab = nullptr) {
+                             int32_t *counts_dev, int cap, const RaggedImg *tab = nullptr, const TileEntry *tiles = nullptr, int T = 0,
+                             int edge_margin = -1) {
     const int cc = ctx->cand_cap;
     // workspace: counts | keys | records | sorted records
     const size_t off_keys = ((size_t)B * 4 + 255) & ~(size_t)255;
@@ -328,7 +382,10 @@ int scrfd_postprocess_launch(fid_ctx *ctx, const HeadViews &hv, int B, int in_h,
     FID_HIP(hipMemsetAsync(cand_count, 0, (size_t)B * 4, ctx->stream));
     const int total_anchors = ((in_h / 8) * (in_w / 8) + (in_h / 16) * (in_w / 16) + (in_h / 32) * (in_w / 32)) * A;
     dim3 g1(cdiv(total_anchors, 256), B);
-    if (tab)
+    if (tiles)
+        hipLaunchKernelGGL(decode_compact_tiled, dim3(g1.x, T), dim3(256), 0, ctx->stream, hv, in_h, in_w, A, conf, tiles, img_h, img_w, edge_margin,
+                           cc, cand_count, keys, data);
+    else if (tab)
         hipLaunchKernelGGL(decode_compact_ragged, g1, dim3(256), 0, ctx->stream, hv, in_h, in_w, A, conf, tab, cc, cand_count, keys, data);
     else
         hipLaunchKernelGGL(decode_compact, g1, dim3(256), 0, ctx->stream, hv, in_h, in_w, A, conf, det_scale, 0, cc, cand_count,
@@ -418,6 +475,39 @@ int fid_scrfd_postprocess_ragged(fid_ctx *ctx, const float *const head_dev[9], c
     FID_TRY(fid::ragged_table(ctx, host.data(), B, &tab));
     return fid::scrfd_postprocess_launch(ctx, hv, B, in_h, in_w, num_anchors, 1, 1, conf_thres, iou_thres, max_num, metric, det_dev,
                                          kps_dev, counts_dev, cap, tab);
+}
+
+// Tiled detection: the heads of T tiles (fid_tile_cut's output through the detector) merged per frame.  tiles: host [T,6], the table
+// fid_tile_cut took; B frames of img_h x img_w.  Sort, NMS, max_num and the capacity report are those of fid_scrfd_postprocess, over B frames.
+int fid_scrfd_postprocess_tiled(fid_ctx *ctx, const float *const head_dev[9], const int32_t pix_stride[9],
+                                const int32_t anc_stride[9], const int64_t batch_stride[9], const int32_t *tiles, int T,
+                                int in_h, int in_w, int num_anchors, int B, int img_h, int img_w, float conf_thres, float iou_thres,
+                                int edge_margin, int max_num, int metric, float *det_dev, float *kps_dev, int32_t *counts_dev, int cap) {
+    FID_REQUIRE(ctx && head_dev && pix_stride && anc_stride && batch_stride && tiles, "NULL argument");
+    FID_REQUIRE(B > 0 && T > 0 && T <= 65535 && cap > 0 && det_dev && kps_dev && counts_dev, "bad batch/tiles/capacity/output");
+    FID_REQUIRE(in_h > 0 && in_w > 0 && in_h % 32 == 0 && in_w % 32 == 0, "input size %dx%d not a multiple of 32", in_w, in_h);
+    FID_REQUIRE(img_h > 0 && img_w > 0 && num_anchors > 0, "bad image size / anchors");
+    FID_REQUIRE(metric == 0 || metric == 1, "metric must be 0 (max) or 1 (default)");
+    HeadViews hv;
+    for (int k = 0; k < 9; k++) {
+        FID_REQUIRE(head_dev[k], "head %d is NULL", k);
+        hv.ptr[k] = head_dev[k];
+        hv.pix_stride[k] = pix_stride[k];
+        hv.anc_stride[k] = anc_stride[k];
+        hv.batch_stride[k] = batch_stride[k];
+    }
+    std::vector<fid::TileEntry> host;
+    int per_frame = 0;
+    FID_TRY(fid::tile_entries(tiles, T, B, img_h, img_w, in_h, in_w, host, &per_frame));
+    const long long total_anchors = ((long long)(in_h / 8) * (in_w / 8) + (long long)(in_h / 16) * (in_w / 16) + (long long)(in_h / 32) * (in_w / 32)) * num_anchors;
+    FID_REQUIRE(per_frame * total_anchors < (1ll << 31), "%d tiles of %lld anchors in one frame overflow the sort key's index", per_frame, total_anchors);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
+    FID_TRY(fid::ensure_dyn_lds(ctx, (const void *)nms_select, (int)fid::nms_lds_bytes(ctx->cand_cap, nullptr)));
+    const fid::TileEntry *tab;
+    FID_TRY(fid::tile_table(ctx, host.data(), T, &tab));
+    return fid::scrfd_postprocess_launch(ctx, hv, B, in_h, in_w, num_anchors, img_h, img_w, conf_thres, iou_thres, max_num, metric, det_dev,
+                                         kps_dev, counts_dev, cap, nullptr, tab, T, edge_margin);
 }
 
 // SCRFD.forward's decode loop alone (scrfd.py:89-119): candidates >= threshold in anchor order

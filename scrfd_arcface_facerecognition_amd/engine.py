@@ -222,6 +222,16 @@ class PostProcessor:
             int(in_hw[1]), int(A), hw.ctypes.data_as(_lib.c_i32_p), float(conf), float(iou), int(max_num),
             int(metric), C.c_void_p(self.det.ptr), C.c_void_p(self.kps.ptr), C.c_void_p(self.counts.ptr), self.cap))
 
+    def run_tiled(self, hv: HeadViews, tiles, B, in_hw, img_hw, conf, iou, edge_margin=8, max_num=0, metric=0, A=2):
+        """run() for tiled detection (fid_scrfd_postprocess_tiled): the heads hold the T tiles of `tiles` (host int32 [T,6], pipeline.tile_plan),
+        det / kps / counts the B frames they were cut from, in frame coordinates; edge_margin < 0 keeps the candidates at a tile's cut edges"""
+        assert B <= self.max_batch
+        tiles = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, 6)
+        check(self.ctx.lib.fid_scrfd_postprocess_tiled(
+            self.ctx.handle, C.cast(hv.ptrs, _lib.c_void_pp), hv.pix, hv.anc, hv.bstride, tiles.ctypes.data_as(_lib.c_i32_p), len(tiles),
+            int(in_hw[0]), int(in_hw[1]), int(A), int(B), int(img_hw[0]), int(img_hw[1]), float(conf), float(iou), int(edge_margin),
+            int(max_num), int(metric), C.c_void_p(self.det.ptr), C.c_void_p(self.kps.ptr), C.c_void_p(self.counts.ptr), self.cap))
+
     def check(self) -> int:
         m = C.c_int()
         check(self.ctx.lib.fid_scrfd_check(self.ctx.handle, C.byref(m)))

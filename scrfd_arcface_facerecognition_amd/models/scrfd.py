@@ -138,6 +138,53 @@ class SCRFD:
                         0 if metric == "max" else 1, self._num_anchors)
         return post.fetch(B)
 
+    # ---- tiled detection: frames larger than the input, seen at native resolution (no reference analogue) ---------------------------------
+    def _detect_chunk_tiled(self, images, max_num, metric, overlap=128, edge_margin=8, overview=True, frames=None):
+        """_detect_chunk with every frame cut into pipeline.tile_plan's tiles: fid_tile_cut, ONE net run over the B * tiles-per-frame tiles
+        (at most max_batch), fid_scrfd_postprocess_tiled -> per frame its detections in frame coordinates.  The post-process's device arrays
+        hold the B frames afterwards, as after _detect_chunk."""
+        from ..pipeline import tile_plan
+        B, H, W, _ = images.shape
+        in_w, in_h = self.input_size
+        tiles = tile_plan(H, W, (in_h, in_w), overlap, overview, B)
+        T = len(tiles)
+        assert T <= self._max_batch, f"{T} tiles exceed max_batch {self._max_batch}"
+        frames = self.ctx.to_device(images) if frames is None else frames
+        det_in = self.ctx.empty((T, in_h, in_w, 3), np.uint8)
+        check(self.ctx.lib.fid_tile_cut(self.ctx.handle, C.c_void_p(frames.ptr), B, H, W, tiles.ctypes.data_as(_lib.c_i32_p), T,
+                                        C.c_void_p(det_in.ptr), in_h, in_w))
+        cn = self._run_net(det_in, T, (in_h, in_w))
+        post = self._postprocessor()
+        post.run_tiled(HeadViews.from_fused(cn), tiles, B, (in_h, in_w), (H, W), self.conf_thres, self.iou_thres, edge_margin, max_num,
+                       0 if metric == "max" else 1, self._num_anchors)
+        return post.fetch(B)
+
+    def tiled_frames_per_chunk(self, H, W, overlap=128, overview=True) -> int:
+        """whole frames of H x W whose tiles fit one detector run of max_batch"""
+        from ..pipeline import tile_plan
+        in_w, in_h = self.input_size
+        per_frame = len(tile_plan(H, W, (in_h, in_w), overlap, overview, 1))
+        if per_frame > self._max_batch:
+            raise ValueError(f"a {W}x{H} frame has {per_frame} tiles at overlap {overlap}: more than max_batch = {self._max_batch}")
+        return self._max_batch // per_frame
+
+    def detect_batch_tiled(self, images, max_num=0, metric="max", overlap=128, edge_margin=8, overview=True):
+        """detect_batch for uniform-size frames larger than the input: images uint8 [B,H,W,3] (or a list of equal shapes) ->
+        [(det[K,5], kpss[K,5,2])] per frame.  Tiles run in chunks of whole frames that fit `max_batch`."""
+        images = np.ascontiguousarray(images, dtype=np.uint8)
+        assert images.ndim == 4 and images.shape[3] == 3, images.shape
+        step = self.tiled_frames_per_chunk(images.shape[1], images.shape[2], overlap, overview)
+        results = []
+        for b0 in range(0, images.shape[0], step):
+            results += self._detect_chunk_tiled(images[b0:b0 + step], max_num, metric, overlap, edge_margin, overview)
+        return results
+
+    def detect_tiled(self, image, max_num=0, metric="max", overlap=128, edge_margin=8, overview=True):
+        """detect() with the frame cut into overlapping native-resolution tiles plus (overview) one letterboxed tile of the whole frame;
+        (det, kpss) as detect returns them.  Faces up to overlap - 2 * edge_margin pixels are found whole by a native tile."""
+        (det, kpss), = self.detect_batch_tiled(np.ascontiguousarray(image, dtype=np.uint8)[None], max_num, metric, overlap, edge_margin, overview)
+        return det, kpss
+
     def detect(self, image, max_num=0, metric="max"):
         """scrfd.py:122-178: (det float32 [K,5], kpss float32 [K,5,2]); K may be 0."""
         (det, kpss), = self._detect_chunk(np.ascontiguousarray(image, dtype=np.uint8)[None], max_num, metric)

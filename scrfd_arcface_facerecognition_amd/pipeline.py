@@ -34,10 +34,53 @@ def shard_range(n_items: int, world: int, rank: int) -> Tuple[int, int]:
     return (rank * n_items) // world, ((rank + 1) * n_items) // world
 
 
+def tile_origins(L: int, n: int, overlap: int) -> List[Tuple[int, int]]:
+    """(origin, extent) of the tiles along one axis of length L for input length n: L <= n -> the single tile (0, L); else origins
+    0, step, 2*step ... (step = n - overlap) while origin + n < L, then a last origin L - n, flush with the far edge; extent n."""
+    L, n, overlap = int(L), int(n), int(overlap)
+    if L <= n:
+        return [(0, L)]
+    step = n - overlap
+    if overlap < 0 or step <= 0:
+        raise ValueError(f"tile_plan: overlap {overlap} must lie in [0, {n})")
+    out, x = [], 0
+    while x + n < L:
+        out.append((x, n))
+        x += step
+    out.append((L - n, n))
+    return out
+
+
+def tile_plan(H: int, W: int, in_hw, overlap: int = 128, overview: bool = True, batch: int = 1) -> np.ndarray:
+    """The tile table of tiled detection (fid_tile_cut / fid_scrfd_postprocess_tiled, include/faceid.h): int32 [T,6], one row
+    `frame, x0, y0, w, h, kind` per tile, for `batch` frames of H x W and a detector input in_hw = (in_h, in_w).
+
+    Per frame: the native tiles (kind 0) are the cross product of `tile_origins` along y and x, y-major -- no tile leaves the frame and the
+    last one of an axis is flush with its far edge --; with `overview` one letterboxed tile (kind 1) that covers the whole frame comes
+    last.  A frame that fits the input (H <= in_h and W <= in_w) gets only that overview row, whatever `overview` says: the untiled path.
+    1920x1080 into 640x640 at overlap 128: x origins [0, 512, 1024, 1280], y origins [0, 440], 8 + 1 tiles; 3840x2160: 8 x 4 + 1 = 33.
+
+    Guarantee: along an axis longer than the input, every integer interval of length s <= overlap - 2 * margin lies inside some tile with
+    `margin` pixels to spare on every interior side of that tile (a side on the frame's boundary needs no spare).  So with the edge rule at
+    `edge_margin = margin`, a face up to overlap - 2 * margin pixels wide and high is found whole by a native tile wherever it stands;
+    larger faces are the overview tile's job."""
+    in_h, in_w = int(in_hw[0]), int(in_hw[1])
+    H, W, batch = int(H), int(W), int(batch)
+    if H <= 0 or W <= 0 or batch <= 0:
+        raise ValueError(f"tile_plan: bad frame size {W}x{H} or batch {batch}")
+    rows = []
+    if H > in_h or W > in_w:
+        ys, xs = tile_origins(H, in_h, overlap), tile_origins(W, in_w, overlap)
+        rows = [(x0, y0, w, h, 0) for y0, h in ys for x0, w in xs]
+    if overview or not rows:
+        rows.append((0, 0, W, H, 1))
+    return np.array([(b,) + r for b in range(batch) for r in rows], dtype=np.int32).reshape(-1, 6)
+
+
 class FacePipeline:
     def __init__(self, ctx: Context, det: CompiledNet, rec: CompiledNet, *, batch: int, faces_per_frame: int = 1,
                  conf_thres: float = 0.5, iou_thres: float = 0.4, metric: int = 0, det_cap: int = 256,
-                 q_buffer=None):
+                 q_buffer=None, tiling=None):
         assert rec.max_batch >= batch * faces_per_frame and det.max_batch >= batch
         self.ctx, self.det, self.rec = ctx, det, rec
         self.B, self.F = int(batch), int(faces_per_frame)
@@ -53,9 +96,39 @@ class FacePipeline:
         self.score = ctx.empty((self.n_slots,), np.float32)
         self._det_in = None
         self._hv: Optional[HeadViews] = None
+        self._set_tiling(tiling)
+
+    def _set_tiling(self, tiling):
+        """tiling: None (every frame is letterboxed whole), or a dict / object with `overlap`, `edge_margin` and `overview` (defaults
+        128, 8, True): detect() cuts every frame into tile_plan's tiles, runs the detector ONCE over the B * tiles-per-frame tiles
+        (det.max_batch must hold them: splitting a step is the caller's choice of B) and merges them per frame on the device."""
+        if tiling is not None:
+            get = tiling.get if isinstance(tiling, dict) else (lambda k, d: getattr(tiling, k, d))
+            tiling = dict(overlap=int(get("overlap", 128)), edge_margin=int(get("edge_margin", 8)), overview=bool(get("overview", True)))
+        self.tiling = tiling
+        self._tile_plans = {}                                  # (H, W) -> tile table
+        self._tile_buf = None
 
     # -- stages ---------------------------------------------------------------------------------
+    def _detect_tiled(self, frames_dev, H, W):
+        ctx, (in_h, in_w) = self.det.ctx, self.in_hw
+        tiles = self._tile_plans.get((H, W))
+        if tiles is None:
+            tiles = self._tile_plans[(H, W)] = tile_plan(H, W, self.in_hw, self.tiling["overlap"], self.tiling["overview"], self.B)
+        T = len(tiles)
+        assert self.det.max_batch >= T, f"tiling: {T} tiles per step exceed the detector's max_batch {self.det.max_batch}"
+        if self._tile_buf is None or self._tile_buf.shape[0] < T:
+            self._tile_buf = ctx.empty((T, in_h, in_w, 3), np.uint8)
+        check(ctx.lib.fid_tile_cut(ctx.handle, _lib._ptr(frames_dev), self.B, H, W, tiles.ctypes.data_as(_lib.c_i32_p), T,
+                                   C.c_void_p(self._tile_buf.ptr), in_h, in_w))
+        self.det.run_device(self._tile_buf, T)
+        if self._hv is None:
+            self._hv = HeadViews.from_fused(self.det)
+        self.post.run_tiled(self._hv, tiles, self.B, self.in_hw, (H, W), self.conf, self.iou, self.tiling["edge_margin"], self.F, self.metric)
+
     def detect(self, frames_dev, H, W):
+        if self.tiling is not None:
+            return self._detect_tiled(frames_dev, H, W)
         in_h, in_w = self.in_hw
         if (H, W) == (in_h, in_w):
             det_in = frames_dev
@@ -277,7 +350,7 @@ class PackedFacePipeline(FacePipeline):
 
     def __init__(self, ctx: Context, det: CompiledNet, rec: CompiledNet, *, batch: int, row_cap: int, max_num: int = 0,
                  rows: str = "capacity", buckets: Optional[Sequence[int]] = None, conf_thres: float = 0.5, iou_thres: float = 0.4,
-                 metric: int = 0, det_cap: int = 256, q_buffer=None):
+                 metric: int = 0, det_cap: int = 256, q_buffer=None, tiling=None):
         assert det.max_batch >= batch and rec.max_batch >= row_cap and 0 < row_cap <= 65535 and max_num >= 0
         if rows not in ("capacity", "count"):
             raise ValueError(f"rows must be 'capacity' or 'count', not {rows!r}")
@@ -301,6 +374,7 @@ class PackedFacePipeline(FacePipeline):
         self.score = ctx.empty((self.row_cap,), np.float32)
         self._det_in = None
         self._hv: Optional[HeadViews] = None
+        self._set_tiling(tiling)                              # (FacePipeline: detect() tiles every frame when set)
         self.n_run = 0                                        # rows the last embed() ran
         self.rec_steps = 0                                    # recogniser runs so far (a step without a face adds none in rows="count")
         self._overflow = 0
