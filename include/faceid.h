@@ -254,6 +254,68 @@ int fid_align_crops_packed(fid_ctx *ctx, const uint8_t *frames_dev, int B, int H
 int fid_align_crops_packed_ragged(fid_ctx *ctx, const uint8_t *frames_dev, size_t frames_bytes, const int32_t *hw, const int64_t *offsets,
                                   int B, const float *kps_dev, int cap, const int32_t *src_dev, int n_rows, uint8_t *crops_dev, double *M_dev);
 
+/* ---- tracking faces across the frames of a video (reference main.py:174-184, two cameras in main2.py:91-99: the loop that detects, embeds and
+ * matches EVERY face of EVERY frame).  A tracker decides on the device, in frame order, which detection continues which track and which faces
+ * need an embedding now: a face that has been named keeps its name and is embedded again only every `refresh` frames.
+ * A tracker is S streams (cameras) x T slots (1 <= T <= FID_TRACK_MAX_SLOTS), all state in device memory.  Per slot: id (int32, -1 = free), box
+ * (the last matched detection), missed (frames since the last match), since (matches since the last embedding), ident_idx / ident_score (the
+ * best gallery match over the track's life; -1 / 0 = unknown).  Per stream: next_id, lost (detections that found no slot).  A free slot has
+ * id = -1 and every other word 0.
+ * One step is  fid_track_step -> the consumers of the row table (fid_align_crops_packed, recogniser, fid_l2_normalize_f16_packed) -> fid_match
+ * -> fid_track_identify;  a second step before the first one's identify, or an identify without a pending step, is FID_E_INVALID.
+ *
+ * fid_track_step.  det_dev [B,cap,5] / counts_dev [B]: as fid_scrfd_postprocess* writes them.  stream: HOST int32 [B], read before the call
+ * returns (like hw of fid_scrfd_postprocess_ragged); stream[b] in [0, S) names the stream of frame b, frames of one stream stand in time order,
+ * stream[b] < 0 skips the frame (no ageing, no rows, outputs -1).  Per stream, over its frames in batch order, k_b = min(max(counts[b], 0), cap):
+ *   detections f = 0 .. k_b - 1 in order.  Candidates: the live tracks not yet matched in this frame (a track started in this frame counts as
+ *     matched).  ovr(track.box, det) is the overlap of the post-process's NMS, operation for operation (areas with +1, intersection clamped at 0,
+ *     correctly rounded divide).  A candidate hits when ovr > iou_thresh (strict: a NaN never hits); the best hit is the maximum ovr, lowest
+ *     slot among equals.
+ *       hit      track.box = det, missed = 0, since += 1; if since >= (known ? refresh : retry) the face is flagged EMBED and since = 0.  known =
+ *                the track had ident_idx >= 0 after the last fid_track_identify (false for a track started during this call).
+ *       no hit   the lowest free slot starts a track: id = next_id++, box = det, missed = since = 0, flags STARTED | EMBED.
+ *       no slot  track id -1, slot -1, lost++, flagged EMBED: an untracked face is embedded every frame and reports its own match.
+ *   end of frame: every live unmatched track gets missed += 1; missed > max_age frees the slot (usable from the stream's next frame on).
+ * Outputs (device): track_dev int32 [B,cap,2] = {track id, slot | FID_TRACK_STARTED | FID_TRACK_EMBED} ({-1,-1}: an untracked face, an entry
+ * f >= k_b, a skipped frame); the row table of the EMBED-flagged faces in (frame, rank) order in fid_face_pack's format: offsets_dev [B+1]
+ * (offsets[B] = total, NOT clipped to row_cap), src_dev [row_cap] (b*cap+f, -1 behind the last row).  A flagged face beyond row_cap is not
+ * embedded this time; its track keeps what it knows and asks again after the interval.
+ *
+ * fid_track_identify.  The step's stream, counts, track, offsets, src and sizes again, plus idx_dev / score_dev [n_rows] as fid_match wrote them
+ * for the first n_rows rows of the table (n_rows = 0 with NULL idx / score: tracking without a gallery).  Per stream and frame, in order:
+ * for the frame's rows i < min(offsets[b+1], n_rows, row_cap): a STARTED face first resets its slot's identity to (-1, 0); then
+ * idx[i] >= 0 && score[i] > ident_score makes (idx[i], score[i]) the slot's identity (the best score over the track's life, the earlier one on
+ * ties).  A STARTED face without a row still resets its slot.  Outputs ident_idx_dev int32 [B,cap] / ident_score_dev float [B,cap]: a tracked
+ * detection gets its slot's identity as it stands after its frame's rows; an untracked one its own row's (idx, score) if it has a row;
+ * everything else (-1, 0).  The identity words of the state belong to this call: between a step and its identify they read as they were
+ * before the step; afterwards a free slot's are 0.
+ *
+ * fid_tracker_reset: stream >= 0 frees that stream's slots and zeroes its next_id / lost (refused while a step is pending); -1 does so for
+ * every stream and drops a pending step.  fid_tracker_read (synchronises; tests and debugging): slots_host int32 [S,T,FID_TRACK_SLOT_WORDS] =
+ * id, missed, since, ident_idx, bits of ident_score, bits of box x1 y1 x2 y2, 0 (reserved); streams_host int32 [S,2] = {next_id, lost}.
+ * FID_E_INVALID, nothing enqueued, outputs untouched: a NULL pointer, S < 1, T outside [1, FID_TRACK_MAX_SLOTS], B <= 0, cap <= 0, B * cap not
+ * fitting int32, row_cap <= 0, iou_thresh NaN or outside [0, 1), max_age < 0, refresh or retry < 1, a stream[b] >= S, n_rows < 0 or > row_cap,
+ * sizes or a stream array that differ from the pending step's.  Both calls are asynchronous on the context's stream and never synchronise
+ * with the host, except once when a step's B outgrows the tracker's per-frame table (1024 frames at first). */
+typedef struct fid_tracker fid_tracker;
+typedef struct fid_track_config {
+    float iou_thresh;              /* [0, 1) */
+    int32_t max_age, refresh, retry;
+} fid_track_config;
+#define FID_TRACK_MAX_SLOTS 64
+#define FID_TRACK_SLOT_WORDS 10
+#define FID_TRACK_STARTED (1 << 8)
+#define FID_TRACK_EMBED (1 << 9)
+int fid_tracker_create(fid_ctx *ctx, int S, int T, fid_tracker **out);
+int fid_tracker_destroy(fid_ctx *ctx, fid_tracker *trk);
+int fid_tracker_reset(fid_ctx *ctx, fid_tracker *trk, int stream);
+int fid_tracker_read(fid_ctx *ctx, fid_tracker *trk, int32_t *slots_host, int32_t *streams_host);
+int fid_track_step(fid_ctx *ctx, fid_tracker *trk, const float *det_dev, const int32_t *counts_dev, const int32_t *stream, int B, int cap,
+                   const fid_track_config *cfg, int32_t *track_dev, int32_t *offsets_dev, int32_t *src_dev, int row_cap);
+int fid_track_identify(fid_ctx *ctx, fid_tracker *trk, const int32_t *counts_dev, const int32_t *stream, int B, int cap,
+                       const int32_t *track_dev, const int32_t *offsets_dev, const int32_t *src_dev, int row_cap, const int32_t *idx_dev,
+                       const float *score_dev, int n_rows, int32_t *ident_idx_dev, float *ident_score_dev);
+
 /* ---- face gates of the reference's product layer: replaces smart_face_recognition.py:1145-1216
  * (assess_face_quality), :1218-1297 (get_face_pose_angles / is_side_face), :1299-1399 (analyze_bbox_for_side_face) and the
  * best-face selection with its four rejections (:1473-1519), for every face of a batch in one launch on the post-process's own

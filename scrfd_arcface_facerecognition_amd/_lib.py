@@ -75,6 +75,15 @@ class GateConfig(C.Structure):
         return cls(**kw)
 
 
+class TrackConfig(C.Structure):
+    """fid_track_config (include/faceid.h): overlap threshold of the association, frames a track survives unmatched, matches between two
+    embeddings of a named track (refresh) and of one without a name (retry)"""
+    _fields_ = [("iou_thresh", C.c_float), ("max_age", C.c_int32), ("refresh", C.c_int32), ("retry", C.c_int32)]
+
+
+TRACK_SLOT_WORDS = 10            # FID_TRACK_SLOT_WORDS
+TRACK_STARTED, TRACK_EMBED = 1 << 8, 1 << 9
+
 SIGNATURES = {
     "fid_abi_version": (C.c_int, []),
     "fid_last_error": (C.c_char_p, []),
@@ -138,6 +147,14 @@ SIGNATURES = {
     "fid_align_crops_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                          C.c_void_p, C.c_void_p]),
     "fid_l2_normalize_f16_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "fid_tracker_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_void_pp]),
+    "fid_tracker_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fid_tracker_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "fid_tracker_read": (C.c_int, [C.c_void_p, C.c_void_p, c_i32_p, c_i32_p]),
+    "fid_track_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i32_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_int]),
+    "fid_track_identify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i32_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "fid_face_gates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
     "fid_gallery_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_void_pp]),

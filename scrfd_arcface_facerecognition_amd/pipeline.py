@@ -383,10 +383,14 @@ class PackedFacePipeline(FacePipeline):
         need = min(int(total), self.row_cap)
         return 0 if need <= 0 else next(v for v in self.buckets if v >= need)
 
+    def _pack(self):
+        """the row table of the last detect(): offsets / src (a subclass may build another table in the same format)"""
+        check(self.ctx.lib.fid_face_pack(self.ctx.handle, C.c_void_p(self.post.counts.ptr), self.B, self.post.cap, self.max_num,
+                                         C.c_void_p(self.offsets.ptr), C.c_void_p(self.src.ptr), self.row_cap))
+
     def embed(self, frames_dev, H, W):
         lib, h = self.ctx.lib, self.ctx.handle
-        check(lib.fid_face_pack(h, C.c_void_p(self.post.counts.ptr), self.B, self.post.cap, self.max_num,
-                                C.c_void_p(self.offsets.ptr), C.c_void_p(self.src.ptr), self.row_cap))
+        self._pack()
         if self.rows == "count":
             total = int(self.ctx.borrow(self.offsets.ptr + 4 * self.B, (1,), np.int32).download()[0])     # the one read-back: synchronises
             self.n_run = self._rows_for(total)
@@ -412,8 +416,7 @@ class PackedFacePipeline(FacePipeline):
         row count the executor has not tuned.  Synchronises."""
         self.detect(frames_dev, H, W)
         lib, h = self.ctx.lib, self.ctx.handle
-        check(lib.fid_face_pack(h, C.c_void_p(self.post.counts.ptr), self.B, self.post.cap, self.max_num,
-                                C.c_void_p(self.offsets.ptr), C.c_void_p(self.src.ptr), self.row_cap))
+        PackedFacePipeline._pack(self)                        # (every face, whatever table a subclass's steps build)
         for n in (self.buckets if self.rows == "count" else [self.row_cap]):
             check(lib.fid_align_crops_packed(h, _lib._ptr(frames_dev), self.B, H, W, C.c_void_p(self.post.kps.ptr), self.post.cap,
                                              C.c_void_p(self.src.ptr), n, C.c_void_p(self.crops.ptr), None))
@@ -462,6 +465,144 @@ class PackedFacePipeline(FacePipeline):
         if kept == 0:
             return np.zeros((0, self.emb_dim), np.float32), offsets
         return self.rec.read(self.rec.low.outputs[0], kept).reshape(kept, -1), offsets
+
+
+class TrackedFacePipeline(PackedFacePipeline):
+    """PackedFacePipeline for video: faces are followed from frame to frame on the device (fid_track_step / fid_track_identify,
+    include/faceid.h) and only the faces whose track is DUE go through alignment, recogniser and match -- a new track, a track without a
+    name every `retry` matches, a named one every `refresh` matches.  Every detection still reports a name: its track's best gallery match
+    so far.  A step's B frames are consecutive frames of the video (of several videos: `stream` of run_step); nothing is read back between
+    the tracker and the recogniser.
+
+    streams     cameras the tracker keeps apart (run_step's `stream[b]` in [0, streams)).
+    max_tracks  slots per stream, 1 .. 64 (default 64: all a wavefront holds; a free slot costs nothing).  A detection that finds no slot
+                is embedded and matched on its own every frame, exactly as PackedFacePipeline treats it.
+    iou         overlap (the NMS's, with its +1 convention) above which a detection continues a track; 0.3 follows a face that moves up
+                to about half its width between two frames and is still below the detector's own NMS threshold 0.4, so two detections
+                that survived NMS in one frame rarely compete for one track.
+    max_age     frames a track survives without a detection (default 15: half a second at 30 fps bridges a turned head or a passer-by
+                without handing the name to the next face that appears in the same place much later).
+    refresh     a NAMED track is embedded again every `refresh` matches (default 16: twice a second at 30 fps.  The name only ever
+                moves to a better score, so refreshing corrects a wrong first match; it is not needed to keep a right one).
+    retry       a track WITHOUT a name is embedded every `retry` matches (default 1: every frame, so an unknown face is never worse
+                off than in PackedFacePipeline).
+    rows / buckets / row_cap behave as in PackedFacePipeline, on the tracker's table; a due face that finds no row keeps what its track
+    knows and asks again after its interval (`overflow`)."""
+
+    def __init__(self, ctx: Context, det: CompiledNet, rec: CompiledNet, *, batch: int, row_cap: int, streams: int = 1, max_tracks: int = 64,
+                 iou: float = 0.3, max_age: int = 15, refresh: int = 16, retry: int = 1, **kw):
+        super().__init__(ctx, det, rec, batch=batch, row_cap=row_cap, **kw)
+        if det.ctx is not ctx:
+            raise ValueError("TrackedFacePipeline: detector and recogniser must share one context / stream")
+        self.streams = int(streams)
+        self.cfg = _lib.TrackConfig(float(iou), int(max_age), int(refresh), int(retry))
+        h = C.c_void_p()
+        check(ctx.lib.fid_tracker_create(ctx.handle, self.streams, int(max_tracks), C.byref(h)))
+        self.tracker, self.max_tracks = h, int(max_tracks)
+        cap = self.post.cap
+        self.track = ctx.empty((self.B, cap, 2), np.int32)
+        self.ident_idx = ctx.empty((self.B, cap), np.int32)
+        self.ident_score = ctx.empty((self.B, cap), np.float32)
+        self._stream = np.zeros(self.B, np.int32)
+        self._identified = True                               # no step is waiting for its identify()
+
+    def _pack(self):
+        check(self.ctx.lib.fid_track_step(self.ctx.handle, self.tracker, C.c_void_p(self.post.det.ptr), C.c_void_p(self.post.counts.ptr),
+                                          self._stream.ctypes.data_as(_lib.c_i32_p), self.B, self.post.cap, C.byref(self.cfg),
+                                          C.c_void_p(self.track.ptr), C.c_void_p(self.offsets.ptr), C.c_void_p(self.src.ptr), self.row_cap))
+        self._identified = False
+
+    def identify(self, n_rows: Optional[int] = None, idx=None, score=None):
+        """fold the match of the last embed()'s rows back into the tracks (n_rows = 0: a step without a gallery or without a face)"""
+        n = self.n_run if n_rows is None else int(n_rows)
+        check(self.ctx.lib.fid_track_identify(self.ctx.handle, self.tracker, C.c_void_p(self.post.counts.ptr),
+                                              self._stream.ctypes.data_as(_lib.c_i32_p), self.B, self.post.cap, C.c_void_p(self.track.ptr),
+                                              C.c_void_p(self.offsets.ptr), C.c_void_p(self.src.ptr), self.row_cap,
+                                              _lib._ptr(self.idx if idx is None else idx) if n else None,
+                                              _lib._ptr(self.score if score is None else score) if n else None, n,
+                                              C.c_void_p(self.ident_idx.ptr), C.c_void_p(self.ident_score.ptr)))
+        self._identified = True
+
+    def match(self, gallery: Optional[Gallery], thresh: float = 0.4, q=None, n=None, idx=None, score=None):
+        """PackedFacePipeline.match, then identify(); gallery None: tracking alone"""
+        n = self.n_run if n is None else n
+        if gallery is None:
+            n = 0
+        super().match(gallery, thresh, q=q, n=n, idx=idx, score=score)
+        self.identify(n, idx, score)
+
+    def run_step(self, frames_dev, H, W, gallery: Optional[Gallery], thresh: float = 0.4, stream=None):
+        """One full pass over one batch of consecutive frames; stream: int [B], the camera of every frame (default: all 0), frames of one
+        camera in time order, -1 = not a frame (it ages no track and gets no row).  Asynchronous when rows="capacity"."""
+        st = np.zeros(self.B, np.int32) if stream is None else np.ascontiguousarray(stream, dtype=np.int32).reshape(-1)
+        if st.shape[0] != self.B:
+            raise ValueError(f"stream has {st.shape[0]} entries for a batch of {self.B}")
+        self._stream = st
+        self.detect(frames_dev, H, W)
+        self.embed(frames_dev, H, W)
+        self.match(gallery, thresh)
+
+    def reset(self, stream: int = -1):
+        """forget the tracks of one stream, or of all (-1: ids start at 0 again)"""
+        check(self.ctx.lib.fid_tracker_reset(self.ctx.handle, self.tracker, int(stream)))
+        if stream < 0:
+            self._identified = True
+
+    def tracker_state(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(slots int32 [streams, max_tracks, 10], per-stream int32 [streams, 2] = next id, lost) -- fid_tracker_read; synchronises"""
+        slots = np.empty((self.streams, self.max_tracks, _lib.TRACK_SLOT_WORDS), np.int32)
+        per_stream = np.empty((self.streams, 2), np.int32)
+        check(self.ctx.lib.fid_tracker_read(self.ctx.handle, self.tracker, slots.ctypes.data_as(_lib.c_i32_p),
+                                            per_stream.ctypes.data_as(_lib.c_i32_p)))
+        return slots, per_stream
+
+    @property
+    def rows_embedded(self) -> int:
+        """rows of the last step's table: the faces that went through the recogniser (reads 4 bytes back)"""
+        total = int(self.ctx.borrow(self.offsets.ptr + 4 * self.B, (1,), np.int32).download()[0])
+        return min(total, self.row_cap)
+
+    # -- results -----------------------------------------------------------------------------------
+    def results_tracked(self, gallery: Optional[Gallery] = None):
+        """Host view of the last step: per frame, for EVERY detection in the detector's order,
+        (bbox[4], det_score, kps[5,2], name, similarity, track id, started) -- name / similarity are the track's (an untracked face's own
+        match; "Unknown" / 0.0 without one), track id -1 = untracked, started = the track began with this detection.  Sets `overflow`."""
+        if not self._identified:
+            raise RuntimeError("TrackedFacePipeline: the last step has not been identified (match() / identify())")
+        self.post.check()
+        counts, det, kps = self.post.counts.download(), self.post.det.download(), self.post.kps.download()
+        track, ii, sc = self.track.download(), self.ident_idx.download(), self.ident_score.download()
+        self._overflow = max(int(self.offsets.download()[self.B]) - self.row_cap, 0)
+        cap = det.shape[1]
+        out = []
+        for b in range(self.B):
+            faces = []
+            for f in range(0 if self._stream[b] < 0 else min(max(int(counts[b]), 0), cap)):
+                j = int(ii[b, f])
+                tid, word = int(track[b, f, 0]), int(track[b, f, 1])
+                faces.append((det[b, f, :4].copy(), float(det[b, f, 4]), kps[b, f].reshape(5, 2).copy(),
+                              gallery.names[j] if j >= 0 and gallery is not None else "Unknown", float(sc[b, f]), tid,
+                              word >= 0 and bool(word & _lib.TRACK_STARTED)))
+            out.append(faces)
+        return out
+
+    def results(self, gallery: Optional[Gallery] = None):
+        """the list FacePipeline.results gives -- (bbox[4], det_score, kps[5,2], name, similarity) -- for every detection, name and
+        similarity taken from its track"""
+        return [[face[:5] for face in frame] for frame in self.results_tracked(gallery)]
+
+    def embeddings(self) -> Tuple[np.ndarray, np.ndarray]:
+        """Raw fp32 embeddings of the rows the last step ran, [rows, 512] in table order, and the table's offsets [B+1] (src says whose)."""
+        offsets = self.offsets.download()
+        kept = min(int(offsets[self.B]), self.row_cap, self.n_run)
+        if kept == 0:
+            return np.zeros((0, self.emb_dim), np.float32), offsets
+        return self.rec.read(self.rec.low.outputs[0], kept).reshape(kept, -1), offsets
+
+    def close(self):
+        if self.tracker:
+            self.ctx.lib.fid_tracker_destroy(self.ctx.handle, self.tracker)
+            self.tracker = None
 
 
 def calibrate_detector_bias(ctx: Context, net, params, frames: np.ndarray, target: int = 48, max_batch: int = 8):

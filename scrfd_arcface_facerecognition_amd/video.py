@@ -11,7 +11,7 @@ import numpy as np
 
 from ._lib import Context, check
 from .engine import Gallery
-from .pipeline import FacePipeline
+from .pipeline import FacePipeline, TrackedFacePipeline
 
 
 class _Pinned:
@@ -31,7 +31,10 @@ class _Pinned:
 
 class StreamRunner:
     """Runs `pipe` over an iterable of uint8 BGR frames of one size, `pipe.B` frames per step, yielding
-    per-frame face lists (FacePipeline.results) in frame order.  Upload of batch i+1 overlaps compute of batch i."""
+    per-frame face lists (FacePipeline.results) in frame order.  Upload of batch i+1 overlaps compute of batch i.
+    An item of the iterable may also be a `(stream_id, frame)` pair -- several cameras in one iterable, each camera's frames in time
+    order --: a TrackedFacePipeline keeps the cameras' tracks apart by it (a bare frame is camera 0) and is told which frames of a ragged
+    last batch are padding, so that they age no track; any other pipeline treats every frame on its own, as before."""
 
     def __init__(self, pipe: FacePipeline, gallery: Gallery, frame_hw, similarity_thresh: float = 0.4):
         self.pipe, self.gallery, self.thr = pipe, gallery, float(similarity_thresh)
@@ -40,6 +43,8 @@ class StreamRunner:
         shape = (pipe.B, self.H, self.W, 3)
         self.host = [_Pinned(ctx, shape, np.uint8) for _ in range(2)]
         self.dev = [ctx.empty(shape, np.uint8) for _ in range(2)]
+        self.tracked = isinstance(pipe, TrackedFacePipeline)
+        self.stream = [np.zeros(pipe.B, np.int32) for _ in range(2)]      # camera of every frame of a staging buffer, -1 = padding
 
     def _upload(self, k: int):
         """copy pinned buffer k -> device buffer k on the upload stream; waits only for the last step that read dev[k]"""
@@ -54,12 +59,17 @@ class StreamRunner:
         def fill(k):
             n = 0
             for f in it:
+                sid = 0
+                if isinstance(f, tuple):
+                    sid, f = f
                 self.host[k].array[n] = f
+                self.stream[k][n] = sid
                 n += 1
                 if n == B:
                     break
             if 0 < n < B:
                 self.host[k].array[n:] = 0          # ragged tail: black frames, their results are dropped
+                self.stream[k][n:] = -1
             return n
 
         cur = 0
@@ -68,7 +78,10 @@ class StreamRunner:
             self._upload(cur)
         while n_cur:
             check(ctx.lib.fid_upload_wait_slot(ctx.handle, cur))   # compute waits for batch `cur` (no host sync)
-            self.pipe.run_step(self.dev[cur], self.H, self.W, self.gallery, self.thr)
+            if self.tracked:
+                self.pipe.run_step(self.dev[cur], self.H, self.W, self.gallery, self.thr, stream=self.stream[cur].copy())
+            else:
+                self.pipe.run_step(self.dev[cur], self.H, self.W, self.gallery, self.thr)
             check(ctx.lib.fid_upload_release(ctx.handle, cur))     # dev[cur] is free again once this step has run
             nxt = cur ^ 1
             n_nxt = fill(nxt)                                       # host fills the other pinned buffer meanwhile
