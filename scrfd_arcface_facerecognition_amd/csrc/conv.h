@@ -137,6 +137,9 @@ int conv_gw_launch(fid_ctx *ctx, const ConvArgs &a, int bm, int bn);
 // kind 2 images packed by lower.py
 int conv_bb_launch(fid_ctx *ctx, const void *in, const void *w1, const float *b1, int ncls1, int act1, const float *s1, const void *w2, const float *b2,
                    void *out, int B, int H, int W, int act2, int rev, int Cp = 64);
+// what conv_bb_launch chooses the form of a plain 64-channel block by (host only): MFMAs per wave of the busiest workgroup in the tile form
+// (conv_bb) and in the walk form (conv_bb_walk); the walk form runs where it is strictly lower, FID_BB_V=1 / 3 force the tile / walk form
+void conv_bb_form_cost(int B, int H, int W, int cus, long long *tile, long long *walk);
 
 // dwpw.hip: depthwise 3x3 (stride 1 | 2, pad 1) + the pointwise 1x1 conv that consumes it, one launch (MobileFaceNet bottlenecks, SCRFD-500M)
 bool dwpw_applicable(int Gp, int Cout_p);

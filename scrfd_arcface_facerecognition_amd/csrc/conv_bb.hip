@@ -777,7 +777,286 @@ __global__ void __launch_bounds__(NW32 * 64, 2) conv_bb32(const BBArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+
+// ======================================================================================================================================
+// The 64-channel block, plain form (bias + ReLU after conv1), WALKING column strips top to bottom ("walk" form).
+// conv_bb's item recomputes at its top the two intermediate rows the tile above it has just computed (conv1 on 16 rows, conv2 on 14), and
+// twelve tiles of 14 cover 168 of 160 rows.  Here a workgroup owns a strip = (image, 14-column band) and walks it downwards; the item
+// structure is conv_bb's: the same 18x18 patch and LDS layout, the same conv_phase, two barriers, the deferred write-out, full drains only.
+//   item s of a strip: OUTPUT rows 16 s - 1 .. 16 s + 14 (row -1 of the first item is never stored).
+//   patch = x rows 16 s - 1 .. 16 s + 16, columns 14 tx - 2 .. + 17 (the halo rows are simply fetched again).
+//   conv1 = the 16 NEW intermediate rows 16 s .. 16 s + 15 (8 per row group, all of them useful) into slots 2 .. 17 of an 18-row
+//           intermediate tile; slot k holds intermediate row 16 s - 2 + k.  Slots 0 and 1 are carried from the item before (zeros in the first
+//           item of a strip: row -1 is conv2's padding, row -2 only feeds the row that is never stored).
+//   conv2 = 16 rows, 8 per row group on all of acc[8], from slots 8 rg .. 8 rg + 9; residual = patch rows 0 .. 15, columns + 2; the staged
+//           tile has 16 rows (exactly four 16-byte stores per thread).
+//   carry (no barrier of its own): the bytes of slots 16 and 17 that belong to cout fragment cw are written by wave (cw, rg = 1) alone, in
+//           its conv1 epilogue, lane by lane.  The SAME lanes copy them to slots 0 and 1 at the top of the next item, behind the top barrier:
+//             source:      written by this lane in the item before and overwritten by this lane in THIS item's conv1 epilogue, which comes later
+//                          in its program (a wave's LDS operations execute in order) -- nobody else writes it;
+//             destination: its previous readers are the rg = 0 waves' conv2 of the item before, complete (lgkmcnt(0)) before they arrived at the
+//                          top barrier; its next readers are conv2 of this item, behind this wave's lgkmcnt(0) and the mid barrier.
+//   strip end: S = cdiv(H + 1, 16) items.  Where the last one holds a single real row (H a multiple of 16, as at 160) it is a REDUCED item: no
+//           conv1 (slot 2 = row H is zero padding, written by the rg = 0 waves), a one-row conv2 on the rg = 0 waves: 18 MFMAs instead of 288.
+// Every output's fp32 sum has conv_bb's order (bias, then chunk, tap column, tap row): the same bits.
+// ======================================================================================================================================
+constexpr int WR = 16;                                           // output rows (and new intermediate rows) per item
+constexpr int WMID_ROWS = WR + 2, WMID_CH = WMID_ROWS * MW * 64, WMID_BYTES = 2 * WMID_CH;      // 36 KB
+constexpr int WST_I = (WR * 16 * CPX) / (NWT * 64);              // 4 stores per thread and item, no surplus
+constexpr int WSTG_BYTES = WR * 16 * ROWB;                       // 32 KB
+// (the fragment rows of conv2's last two pixel columns run one or two pixels past a row: the 512 bytes behind the tile, as in conv_bb; no bias table)
+constexpr int OFFW_MID = OFF_SPARE + 1024, OFFW_STG = OFFW_MID + WMID_BYTES + 512, LDSW_BYTES = OFFW_STG + WSTG_BYTES;
+static_assert(LDSW_BYTES <= 160 * 1024 && WST_I * NWT * 64 == WR * 16 * CPX, "LDS budget; whole store rounds");
+constexpr int WALK_MFMA = 288, WALK_MFMA_REDUCED = 18, TILE_MFMA = 270;      // per wave and item (a reduced item: the rg = 0 waves)
+
+struct BBWalkArgs {
+    const void *in;
+    const void *w1, *w2;      // as BBArgs
+    const float *b1, *b2;     // fp32 [64] each
+    void *out;
+    int H, W;
+    int act2;
+    int tiles_x, n_strips;    // 14-column bands per image; strips = B x bands
+    int S;                    // items per strip
+    int reduced_last;         // the last item of a strip holds one real row
+    FastDiv d_tx;
+    unsigned io_bytes;
+    int rev;                  // ConvArgs::rev: the order of the strips (a strip itself always runs top-down)
+};
+
+__global__ void __launch_bounds__(NWT * 64, 2) conv_bb_walk(const BBWalkArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int cw = wave & 3, rg = wave >> 2;
+    const int frow = lane & 15, fq = lane >> 4;
+    const int bid = xcd_major_id(blockIdx.x, gridDim.x);
+    const int my_strips = bid < a.n_strips ? (a.n_strips - 1 - bid) / gridDim.x + 1 : 0;
+    if (my_strips == 0) return;
+    const int my_items = my_strips * a.S;
+
+    auto decode_strip = [&](int strip, int &n, int &tx) {
+        if (a.rev) strip = a.n_strips - 1 - strip;
+        n = fastdiv(strip, a.d_tx);
+        tx = strip - n * a.tiles_x;
+    };
+    const auto rs_in = __builtin_amdgcn_make_buffer_rsrc((void *)a.in, 0, a.io_bytes, 0x00020000);
+    const auto rs_out = __builtin_amdgcn_make_buffer_rsrc((void *)a.out, 0, a.io_bytes, 0x00020000);
+
+    // ---- my pieces of an item's patch (conv_bb's): piece j = wave + 8k -> chunk j / 21, pixels 16 (j % 21) .. +15, four lanes per pixel
+    int p_pk[MAX_P];                                            // py | px << 8 | channel offset (halfs) << 16; py = 255: nothing to fetch
+#pragma unroll
+    for (int k = 0; k < MAX_P; k++) {
+        const int j = wave + NWT * k;
+        const int ch = j / P_BLKS, blk = j - ch * P_BLKS;
+        const int row = blk * 16 + (lane >> 2);
+        int py = row / PW;
+        const int px = row - py * PW;
+        if (row >= NPIX || j >= N_PIECES) py = 255;
+        p_pk[k] = py | (px << 8) | (((((lane & 3) ^ swz64(row)) * 8) + ch * 32) << 16);
+    }
+    // piece k of the patch of item s of strip (n, tx) into buffer `buf` (live = false: a piece of zeros)
+    auto issue_piece = [&](int k, int n, int s, int tx, bool live, int buf) {
+        const int y0 = s * WR - 1, x0 = tx * TO - 2;
+        const int j = wave + NWT * k;
+        int pk = p_pk[k];
+        asm volatile("" : "+v"(pk));                            // opaque: unpack at the use
+        const int py = pk & 255, iy = y0 + py, ix = x0 + ((pk >> 8) & 255);
+        const bool in = live && py != 255 && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
+        const unsigned vo = in ? (unsigned)((((n * a.H + iy) * a.W + ix) * 64 + (pk >> 16)) * 2) : OOB;
+        char *d = j < N_PIECES ? smem + OFF_X + buf * X_ITEM + j * 1024 : smem + OFF_SPARE;   // surplus piece: zeros into the spare KB
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (__attribute__((address_space(3))) void *)d, 16, vo, 0, 0, 0);
+    };
+    int strip = bid, s = 0, n, tx;
+    decode_strip(strip, n, tx);
+#pragma unroll
+    for (int k = 0; k < MAX_P; k++) issue_piece(k, n, 0, tx, true, 0);
+
+    // ---- both filter banks of my 16 couts: kind 2 = [chunk][cout fragment 0..7][dx][dy][lane] x 16 B
+    half8 w1[18], w2[18];                                       // [chunk * 9 + dy * 3 + dx]
+    {
+        const char *p1 = (const char *)a.w1 + cw * 9216 + lane * 16, *p2 = (const char *)a.w2 + cw * 9216 + lane * 16;
+#pragma unroll
+        for (int ck = 0; ck < 2; ck++)
+#pragma unroll
+            for (int dx = 0; dx < 3; dx++)
+#pragma unroll
+                for (int dy = 0; dy < 3; dy++) {
+                    w1[ck * 9 + dy * 3 + dx] = *(const half8 *)(p1 + ck * (8 * 9216) + dx * 3072 + dy * 1024);
+                    w2[ck * 9 + dy * 3 + dx] = *(const half8 *)(p2 + ck * (8 * 9216) + dx * 3072 + dy * 1024);
+                }
+    }
+    const f32x4 bias1 = *(const f32x4 *)(a.b1 + cw * 16 + fq * 4), bias2 = *(const f32x4 *)(a.b2 + cw * 16 + fq * 4);
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int i = 0; i < 18; i++) asm volatile("" : "+v"(w1[i]), "+v"(w2[i]));
+
+    int pbase[2][4];                                            // pixel fragment addresses: conv_bb's scheme
+#pragma unroll
+    for (int par = 0; par < 2; par++)
+#pragma unroll
+        for (int c = 0; c < 4; c++) pbase[par][c] = frow * 64 + ((fq ^ ((((frow + par) >> 1) + c) & 3)) << 4);
+
+    f32x4 acc[8];
+    constexpr int PD = BB_PD;
+    // conv_bb's conv_phase: ROWS output rows of this wave from ROWS + 2 fragment rows x 3 tap columns x 2 chunks, one flattened sequence read PD rows ahead
+    auto conv_phase = [&](int base_off, auto rows_tag, auto pw_tag, auto cs_tag, const half8 *wv, auto &&col_hook) {
+        constexpr int ROWS = decltype(rows_tag)::value, PWV = decltype(pw_tag)::value, CS = decltype(cs_tag)::value, PH = ROWS + 2, NQ = 6 * PH;
+        int pb[2][4];
+#pragma unroll
+        for (int par = 0; par < 2; par++)
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                pb[par][c] = pbase[par][c] + base_off;
+                asm volatile("" : "+v"(pb[par][c]));
+            }
+        half8 pq[PD + 1];
+        auto load_p = [&](int q) {                              // q = (chunk * 3 + dx) * PH + fragment row
+            const int pass = q / PH, r = q - pass * PH, ck = pass / 3, dx = pass - ck * 3;
+            const int K = r * PWV + dx;
+            pq[q % (PD + 1)] = *(const half8 *)(smem + (pb[K & 1][(K >> 1) & 3] + (K * 64 + ck * CS)));
+        };
+#pragma unroll
+        for (int q = 0; q < PD; q++) load_p(q);
+#pragma unroll
+        for (int q = 0; q < NQ; q++) {
+            const int pass = q / PH, r = q - pass * PH, ck = pass / 3, dx = pass - ck * 3;
+            if (r == 0) col_hook(pass);
+            if (q + PD < NQ) load_p(q + PD);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int dy = 0; dy < 3; dy++) {
+                const int mi = r - dy;
+                if (mi < 0 || mi >= ROWS) continue;
+                acc[mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wv[ck * 9 + dy * 3 + dx], pq[q % (PD + 1)], acc[mi], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    using std::integral_constant;
+
+    // write-out of the rows staged by the item before (item ps of strip (pn, ptx); pn < 0: none): 16-byte slot g = i * 512 + thread =
+    // (pixel g / 8, chunk g % 8), 64 pixels = 4 staged rows per round.  Staged row r is output row 16 ps - 1 + r: row -1 and the rows
+    // from H on (all but the first of a reduced item, which staged one row) are not stored.
+    auto write_out = [&](int pn, int ps, int ptx) {
+        int t2 = tid;
+        asm volatile("" : "+v"(t2));
+        const int q0 = t2 >> 3, c = t2 & 7;
+        const int pr0 = q0 >> 4, pc = q0 & 15;
+        const int oy0 = ps * WR - 1, ox = ptx * TO + pc;
+        const bool okc = pn >= 0 && pc < TO && ox < a.W;
+        const char *lsrc = smem + OFFW_STG + q0 * ROWB + (((c + pc) % CPX) << 4);
+        const unsigned g0 = (unsigned)((((pn * a.H + oy0 + pr0) * a.W + ox) * 64 + c * 8) * 2);
+        const unsigned rstride = (unsigned)(a.W * 64 * 2);
+#pragma unroll
+        for (int i = 0; i < WST_I; i++) {
+            const bool ok = okc && (unsigned)(oy0 + 4 * i + pr0) < (unsigned)a.H;
+            const u32x4 v = *(const u32x4 *)(lsrc + i * (64 * ROWB));
+            __builtin_amdgcn_raw_buffer_store_b128(v, rs_out, ok ? g0 + (unsigned)(4 * i) * rstride : OOB, 0, 0);
+        }
+    };
+    auto no_hook = [](int) {};
+
+    int pn = -1, ps = 0, ptx = 0;
+    for (int it = 0; it < my_items; it++) {
+        const int buf = it & 1;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        raw_barrier();                                          // everybody's pieces; the rows of the item before are staged; its patch buffer and slots 0 / 1 are free
+        write_out(pn, ps, ptx);
+        // the walk: the next item of this strip, then the first item of my next strip
+        const bool nlive = it + 1 < my_items;
+        int ns = s + 1, nstrip = strip;
+        if (ns == a.S) { ns = 0; nstrip += gridDim.x; }
+        int nn, ntx;
+        decode_strip(nlive ? nstrip : 0, nn, ntx);
+        auto fetch_hook = [&](int pass) { issue_piece(pass, nn, ns, ntx, nlive, buf ^ 1); };      // one piece of the next patch per (chunk, column) pass
+        const bool reduced = a.reduced_last && s == a.S - 1;
+
+        int lo = lane;
+        asm volatile("" : "+v"(lo));
+        const int fr = lo & 15, q4 = lo >> 4;
+        // my lane's bytes of an intermediate pixel row: slot k at + k * (MW * 64)
+        char *mp = smem + OFFW_MID + (cw >> 1) * WMID_CH + fr * 64 + ((((cw & 1) * 2 + (q4 >> 1)) ^ swz64(fr)) << 4) + (q4 & 1) * 8;
+        if (rg == 1) {                                          // the carry (header comment): slots 16 / 17 of the item before -> slots 0 / 1; a new strip starts from zeros
+            half4 c0 = *(const half4 *)(mp + 16 * (MW * 64)), c1 = *(const half4 *)(mp + 17 * (MW * 64));
+            if (s == 0) c0 = c1 = half4{0, 0, 0, 0};
+            *(half4 *)mp = c0;
+            *(half4 *)(mp + MW * 64) = c1;
+        }
+
+        if (!reduced) {
+            // ================= A: conv1 on the 16 new intermediate rows (rows 16 s + 8 rg .. + 7 here: slots 2 + 8 rg .. 9 + 8 rg) =================
+#pragma unroll
+            for (int r = 0; r < 8; r++) acc[r] = bias1;
+            conv_phase(OFF_X + buf * X_ITEM + rg * (8 * PW * 64), integral_constant<int, 8>{}, integral_constant<int, PW>{}, integral_constant<int, P_BYTES>{}, w1, fetch_hook);
+            // intermediate pixel (slot 2 + 8 rg + i, column fr) = image pixel (16 s + 8 rg + i, tx*14 - 1 + fr); outside the image it is conv2's
+            // zero padding, NOT conv1 evaluated there (no row is above the image: only the left, right and bottom edges clear anything)
+            const int gx = tx * TO - 1 + fr, gy0 = s * WR + rg * 8;
+            const bool xin = (unsigned)gx < (unsigned)a.W;
+            const bool edge = tx == 0 || s * WR + WR > a.H || tx * TO + 15 > a.W;
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                half4 h = __builtin_elementwise_max(__builtin_convertvector(acc[i], half4), half4{0, 0, 0, 0});
+                if (edge && !(xin && gy0 + i < a.H)) h = half4{0, 0, 0, 0};
+                *(half4 *)(mp + (2 + rg * 8 + i) * (MW * 64)) = h;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < MAX_P; k++) issue_piece(k, nn, ns, ntx, nlive, buf ^ 1);
+            if (rg == 0) *(half4 *)(mp + 2 * (MW * 64)) = half4{0, 0, 0, 0};      // row H
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        raw_barrier();                                          // the intermediate tile is complete (and everyone has read the staged rows of the item before)
+
+        // ================= B: conv2 on output rows 16 s - 1 + 8 rg .. + 7 (slots 8 rg .. 8 rg + 9); residual = patch rows 8 rg .. + 7, columns + 2 =================
+        const int g0 = (cw & 1) * 2 + (q4 >> 1);
+        const char *xp = smem + OFF_X + buf * X_ITEM + (cw >> 1) * P_BYTES + (q4 & 1) * 8;
+        char *sp = smem + OFFW_STG + fr * ROWB + (((cw * 2 + (q4 >> 1) + fr) % CPX) << 4) + (q4 & 1) * 8;   // chunk rotated by the pixel column
+        if (!reduced) {
+#pragma unroll
+            for (int r = 0; r < 8; r++) acc[r] = bias2;
+            conv_phase(OFFW_MID + rg * (8 * MW * 64), integral_constant<int, 8>{}, integral_constant<int, MW>{}, integral_constant<int, WMID_CH>{}, w2, no_hook);
+            half4 rs[8];                                        // all residual reads first: one LDS round trip
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const int lin = (rg * 8 + i) * PW + fr + 2;
+                rs[i] = *(const half4 *)(xp + lin * 64 + ((g0 ^ swz64(lin)) << 4));
+            }
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                f32x4 v = acc[i] + __builtin_convertvector(rs[i], f32x4);
+                half4 h = __builtin_convertvector(v, half4);
+                if (a.act2 == ACT_RELU) h = __builtin_elementwise_max(h, half4{0, 0, 0, 0});
+                *(half4 *)(sp + (rg * 8 + i) * (16 * ROWB)) = h;
+            }
+        } else if (rg == 0) {                                   // the one real row (H - 1) from slots 0 .. 2
+            acc[0] = bias2;
+            conv_phase(OFFW_MID, integral_constant<int, 1>{}, integral_constant<int, MW>{}, integral_constant<int, WMID_CH>{}, w2, no_hook);
+            const int lin = fr + 2;
+            const half4 r0 = *(const half4 *)(xp + lin * 64 + ((g0 ^ swz64(lin)) << 4));
+            f32x4 v = acc[0] + __builtin_convertvector(r0, f32x4);
+            half4 h = __builtin_convertvector(v, half4);
+            if (a.act2 == ACT_RELU) h = __builtin_elementwise_max(h, half4{0, 0, 0, 0});
+            *(half4 *)sp = h;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        pn = n; ps = s; ptx = tx;
+        s = ns; strip = nstrip; n = nn; tx = ntx;
+    }
+    raw_barrier();                                              // the last rows are staged
+    write_out(pn, ps, ptx);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the surplus pieces target this workgroup's LDS: drain before exit
+}
+
 }  // namespace
+
+// MFMAs per wave of the busiest workgroup, tile form (conv_bb: 14x14 tiles dealt over the CUs) and walk form (conv_bb_walk: whole strips
+// dealt over the CUs): what conv_bb_launch chooses by.  Host only.
+void conv_bb_form_cost(int B, int H, int W, int cus, long long *tile, long long *walk) {
+    const int tiles_x = cdiv(W, TO), S = cdiv(H + 1, WR);
+    const long long per_strip = H % WR == 0 ? (long long)(S - 1) * WALK_MFMA + WALK_MFMA_REDUCED : (long long)S * WALK_MFMA;
+    *tile = cdiv64((int64_t)B * tiles_x * cdiv(H, TO), cus) * TILE_MFMA;
+    *walk = cdiv64((int64_t)B * tiles_x, cus) * per_strip;
+}
 
 // x [B, H, W, Cp] fp16 -> out [B, H, W, Cp], Cp = 64 | 32 stored channels; w1 / w2: repack kind 2 images (147 456 B | 73 728 B each), b1 fp32 [ncls1][64], b2 fp32 [64], s1 fp32 [64] or NULL
 int conv_bb_launch(fid_ctx *ctx, const void *in, const void *w1, const float *b1, int ncls1, int act1, const float *s1, const void *w2, const float *b2,
@@ -820,6 +1099,25 @@ int conv_bb_launch(fid_ctx *ctx, const void *in, const void *w1, const float *b1
         }
         FID_HIP(hipGetLastError());
         return FID_OK;
+    }
+    // The plain form also exists as conv_bb_walk (column strips walked top-down, no recomputed rows).  FID_BB_V=1 forces the tile form below,
+    // FID_BB_V=3 the walk form; otherwise the form whose busiest workgroup executes fewer MFMAs per wave (conv_bb_form_cost; a tie keeps the
+    // tile form): 64 x 160x160 on 256 CUs is 36 x 270 = 9 720 against 3 x 2 898 = 8 694; at batch 8 the 96 strips would leave most CUs idle.
+    if (ncls1 == 1 && act1 == ACT_RELU && !(bv && atoi(bv) == 1) && !ablate) {      // (the FID_BB_ABLATE experiments are the tile form's)
+        long long tile_cost, walk_cost;
+        conv_bb_form_cost(B, H, W, ctx->num_cus, &tile_cost, &walk_cost);
+        if ((bv && atoi(bv) == 3) || walk_cost < tile_cost) {
+            BBWalkArgs wa{};
+            wa.in = in; wa.w1 = w1; wa.w2 = w2; wa.b1 = b1; wa.b2 = b2; wa.out = out;
+            wa.H = H; wa.W = W; wa.act2 = act2; wa.rev = rev;
+            wa.tiles_x = a.tiles_x; wa.n_strips = B * a.tiles_x; wa.d_tx = a.d_tx;
+            wa.S = cdiv(H + 1, WR); wa.reduced_last = H % WR == 0;
+            wa.io_bytes = a.io_bytes;
+            FID_TRY(ensure_dyn_lds(ctx, (const void *)conv_bb_walk, LDSW_BYTES));
+            hipLaunchKernelGGL(conv_bb_walk, dim3(std::min(wa.n_strips, ctx->num_cus)), dim3(NWT * 64), LDSW_BYTES, ctx->stream, wa);
+            FID_HIP(hipGetLastError());
+            return FID_OK;
+        }
     }
     const int grid = std::min(a.n_tiles, ctx->num_cus);
     if (ncls1 == 9 || act1 == ACT_PRELU) {
