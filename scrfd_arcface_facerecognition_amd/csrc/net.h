@@ -1,4 +1,4 @@
-// Layer-table format shared with scrfd_arcface_facerecognition_amd/lower.py (keep in sync).
+// Layer-table format shared with lower.py through its mirror scrfd_arcface_facerecognition_amd/net_layout.py (kept in sync by tests/test_net_layout.py).
 #pragma once
 #include "conv.h"
 

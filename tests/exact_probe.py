@@ -36,6 +36,7 @@ import torch.nn.functional as F
 
 from oracle import align, nets as onets
 from scrfd_arcface_facerecognition_amd.archs import Conv, Net
+from scrfd_arcface_facerecognition_amd.lower import OP_DWCONV, T_CP, T_H, T_W, W_DST, W_KH, W_KW, W_PAD, W_SRC, W_TYPE
 
 IN_MEAN, IN_SCALE = 127.5, 2.0        # the first conv reads 2 p - 255 with weights W * in_scale / 2 = W (lower.py): exact as well
 PIXELS = (120, 136)                   # |2 p - 255| <= 15
@@ -1007,16 +1008,16 @@ def split_mirror(M, cin_p, cout_p, taps, cus, force=None, allow_split=True):
 def conv_geometry(low, name, batch):
     """(M, Cin_p, Cout_p, taps) of the OP_CONV record `name` of a lowered net, as csrc/net.hip run_op hands them to conv_plan"""
     r = low.ops[low.op_names.index(name)]
-    src, dst = low.tensors[int(r[1])], low.tensors[int(r[2])]
-    return batch * int(dst[2]) * int(dst[3]), int(src[1]), int(dst[1]), int(r[4]) * int(r[5])
+    src, dst = low.tensors[int(r[W_SRC])], low.tensors[int(r[W_DST])]
+    return batch * int(dst[T_H]) * int(dst[T_W]), int(src[T_CP]), int(dst[T_CP]), int(r[W_KH]) * int(r[W_KW])
 
 
 def takes_gdc_rows(low, name):
     """csrc/net.hip OP_DWCONV: the record `name` meets the condition under which gdc_rows runs instead of dwconv_nhwc"""
     r = low.ops[low.op_names.index(name)]
-    src, dst = low.tensors[int(r[1])], low.tensors[int(r[2])]
-    return (int(r[0]) == 4 and int(r[4]) == int(r[5]) <= 8 and int(r[7]) == 0 and int(src[2]) == int(r[4]) and int(src[3]) == int(r[5])
-            and int(dst[2]) == 1 and int(dst[3]) == 1)
+    src, dst = low.tensors[int(r[W_SRC])], low.tensors[int(r[W_DST])]
+    return (int(r[W_TYPE]) == OP_DWCONV and int(r[W_KH]) == int(r[W_KW]) <= 8 and int(r[W_PAD]) == 0 and int(src[T_H]) == int(r[W_KH])
+            and int(src[T_W]) == int(r[W_KW]) and int(dst[T_H]) == 1 and int(dst[T_W]) == 1)
 
 
 # ---- split-K probes: the family nets under a forced split, and a 1x1 conv with an up-sampled residual ---------------------------------------

@@ -5,11 +5,8 @@ arithmetic is pure Python on lower()'s tensor table, so tests/test_slot_guard_cp
 import numpy as np
 
 from scrfd_arcface_facerecognition_amd.archs import Conv, Net
-from scrfd_arcface_facerecognition_amd.lower import OP_CONV, OP_LATFPN, OP_STEMBLOCK
-
-
-# words of an op record that name a second tensor (csrc/net.h)
-W_TYPE, W_DST, W_X_DST2, W_L_LAT, W_S_DST2, W_X_SRC2, W_X_W2OFF, T_SLOT = 0, 2, 20, 22, 24, 23, 29, 5
+from scrfd_arcface_facerecognition_amd.lower import (OP_CONV, OP_LATFPN, OP_STEMBLOCK, T_CP, T_DTYPE, T_H, T_SLOT, T_W, W_DST, W_L_LAT, W_S_DST2, W_TYPE,
+                                                     W_X_DST2, W_X_SRC2, W_X_W2OFF)
 
 
 def _row(name, tup, env, **match):
@@ -82,11 +79,11 @@ POISON = {"max": 0x7BFF, "nan": 0x7E00}
 
 
 def slot_table(low):
-    """(slot of every tensor, bytes per image of every tensor, bytes per image of every slot) from lower()'s tensor table.  Column 5 is the
+    """(slot of every tensor, bytes per image of every tensor, bytes per image of every slot) from lower()'s tensor table.  T_SLOT is the
     slot (a view's record already names its base's slot), a tensor's image is H x W x Cp elements of 2 (fp16) or 4 (fp32, dtype 1) bytes,
     every tensor of a slot starts at the slot's base, and a slot's image is the largest of its tensors' (csrc/net.hip, fid_net_create)."""
     t_slot, t_bytes, s_bytes = [], [], {}
-    for C_, Cp, H, W, dtype, slot, _, _ in (tuple(int(v) for v in r) for r in low.tensors):
+    for Cp, H, W, dtype, slot in (tuple(int(r[w]) for w in (T_CP, T_H, T_W, T_DTYPE, T_SLOT)) for r in low.tensors):
         b = H * W * Cp * (4 if dtype == 1 else 2)
         t_slot.append(slot)
         t_bytes.append(b)
@@ -111,7 +108,7 @@ def own_data_tensors(low):
         for op, word in ((OP_CONV, W_X_DST2), (OP_STEMBLOCK, W_S_DST2), (OP_LATFPN, W_L_LAT)):     # second outputs: tensor id + 1
             if kind == op and r[word] > 0:
                 dsts.append(int(r[word]) - 1)
-        maybe_skipped = kind == OP_CONV and r[W_X_SRC2] == 0 and r[W_X_W2OFF] > 0                 # word 29 of a shortcut op: its consumer + 1
+        maybe_skipped = kind == OP_CONV and r[W_X_SRC2] == 0 and r[W_X_W2OFF] > 0                 # this word of a shortcut op: its consumer + 1
         for d in dsts:
             last[int(low.tensors[d][T_SLOT])] = None if maybe_skipped else d
     return sorted(names[d] for d in last.values() if d is not None)

@@ -139,7 +139,7 @@ def test_bn_probe_lowers_to_ideal_constants(key, monkeypatch):
     assert diff.size == 0, (key, f"{diff.size} bytes differ, first at {diff[:4].tolist()}")
     assert np.array_equal(real.ops, ideal.ops)
     ops = {nm: r for nm, r in zip(real.op_names, real.ops)}
-    kinds = [int(r[0]) for r in real.ops]
+    kinds = [int(r[lower.W_TYPE]) for r in real.ops]
     if key in ep.FAMILY_BN_KEYS.values():
         want = {"c": lower.OP_CONV, "r": lower.OP_CONV}
     elif key in ep.IR_KEYS.values():
@@ -147,13 +147,13 @@ def test_bn_probe_lowers_to_ideal_constants(key, monkeypatch):
         assert len(real.ops) == 2 and "b.conv1" not in real.tensor_id
     elif key in ep.SHORTCUT_BN_KEYS.values():
         want = {"b.conv1": lower.OP_CONV}
-        assert int(ops["b.conv2"][23]) > 0 and not int(ops["b.conv2"][11]) & lower.CF_BORDER        # (the shortcut's second weight image)
+        assert int(ops["b.conv2"][lower.W_X_SRC2]) > 0 and not int(ops["b.conv2"][lower.W_FLAGS]) & lower.CF_BORDER        # (the shortcut's second weight image)
     else:
         want = {"b.conv1": lower.OP_STEMBLOCK}
         assert kinds[0] == lower.OP_STEMBLOCK and "stem.even" in real.tensor_id and "stem" not in real.tensor_id
     for nm, kind in want.items():
-        assert int(ops[nm][0]) == kind and int(ops[nm][11]) & lower.CF_BORDER, (key, nm, real.op_names)
-    assert sum(bool(int(r[11]) & lower.CF_BORDER) for r in real.ops) == len(want)
+        assert int(ops[nm][lower.W_TYPE]) == kind and int(ops[nm][lower.W_FLAGS]) & lower.CF_BORDER, (key, nm, real.op_names)
+    assert sum(bool(int(r[lower.W_FLAGS]) & lower.CF_BORDER) for r in real.ops) == len(want)
 
 
 def test_comparator_details():
@@ -219,7 +219,7 @@ def _split_geometry(key, name, monkeypatch):
     from scrfd_arcface_facerecognition_amd import lower
     probe = ep.PROBES[key]()
     low = lower.lower(probe.net, probe.P)
-    assert int(low.ops[low.op_names.index(name)][0]) == lower.OP_CONV
+    assert int(low.ops[low.op_names.index(name)][lower.W_TYPE]) == lower.OP_CONV
     return probe, low, ep.conv_geometry(low, name, probe.batch)
 
 
@@ -235,7 +235,7 @@ def test_split_cases_split_as_they_say(key, names, force, slabs, monkeypatch):
         for cus in (64, 256, 304):
             m = ep.split_mirror(M, cin_p, cout_p, taps, cus, f)
             assert len(m["slabs"]) > 1 and sum(m["slabs"]) == m["ksteps"] and (slabs is None or m["slabs"] == slabs), (name, cus, m)
-        flags = int(low.ops[low.op_names.index(name)][11])
+        flags = int(low.ops[low.op_names.index(name)][lower.W_FLAGS])
         assert bool(flags & lower.CF_BORDER) == key.startswith("convbn") and bool(flags & lower.CF_RES_UP2) == key.startswith("up2")
         n = next(x for x in probe.net.nodes if x.name == name)
         first_of_last = sum(m["slabs"][:-1])
@@ -284,13 +284,13 @@ def test_fc_probe_lowers_to_ideal_constants(key, monkeypatch):
     ideal = lower.lower(probe.net, probe.P)
     assert real.blob == ideal.blob and np.array_equal(real.ops, ideal.ops)
     op = real.ops[real.op_names.index("fc")]
-    src, dst = real.tensors[int(op[1])], real.tensors[int(op[2])]
+    src, dst = real.tensors[int(op[lower.W_SRC])], real.tensors[int(op[lower.W_DST])]
     _, W, b = ep.fc_columns(n, ref, probe.P)
     K = W.shape[1]
-    assert int(op[0]) == lower.OP_CONV and int(dst[4]) == 1 and (int(src[0]), int(src[1]), int(src[2]), int(src[3])) == (K, K, 1, 1)
-    got = np.frombuffer(real.blob, np.float16, count=int(op[17]) * K, offset=int(op[13])).reshape(int(op[17]), K)
+    assert int(op[lower.W_TYPE]) == lower.OP_CONV and int(dst[lower.T_DTYPE]) == 1 and tuple(int(src[w]) for w in (lower.T_C, lower.T_CP, lower.T_H, lower.T_W)) == (K, K, 1, 1)
+    got = np.frombuffer(real.blob, np.float16, count=int(op[lower.W_WROWS]) * K, offset=int(op[lower.W_WOFF])).reshape(int(op[lower.W_WROWS]), K)
     assert np.array_equal(got[:n.cout].astype(np.float64), W) and not got[n.cout:].any()
-    assert np.array_equal(np.frombuffer(real.blob, np.float32, count=n.cout, offset=int(op[15])).astype(np.float64), b)
+    assert np.array_equal(np.frombuffer(real.blob, np.float32, count=n.cout, offset=int(op[lower.W_BOFF])).astype(np.float64), b)
     assert (ref["b"] < 0).any() and (ref["b"] > 0).any()
 
 
@@ -303,7 +303,7 @@ def test_fused_stem_probe(key, monkeypatch):
     monkeypatch.delenv("FID_NO_STEM_FUSE", raising=False)
     assert lower.lower(probe.net, probe.P).op_names == ["stem.fused"] and [n.name for n in held] == ["stem.2"]
     monkeypatch.setenv("FID_NO_STEM_FUSE", "1")
-    assert [int(r[0]) for r in lower.lower(probe.net, probe.P).ops] == [lower.OP_STEM, lower.OP_CONV, lower.OP_CONV, lower.OP_MAXPOOL]
+    assert [int(r[lower.W_TYPE]) for r in lower.lower(probe.net, probe.P).ops] == [lower.OP_STEM, lower.OP_CONV, lower.OP_CONV, lower.OP_MAXPOOL]
     pool = probe.net.nodes[-1]
     Hp, Wp = ref["stem.pool"].shape[1:3]
     assert Hp % 8 != 0 or Hp % 6 != 0                        # ragged row tiles in one of the two forms at least
@@ -321,7 +321,7 @@ def test_first_conv_probe_lowers_to_the_stem_op(key):
     probe = ep.PROBES[key]()
     low = lower.lower(probe.net, probe.P)
     n = probe.net.nodes[0]
-    assert [int(r[0]) for r in low.ops] == [lower.OP_STEM] and int(low.tensors[0][1]) == (n.cout + 31) // 32 * 32 and int(low.ops[0][6]) == n.stride
+    assert [int(r[lower.W_TYPE]) for r in low.ops] == [lower.OP_STEM] and int(low.tensors[0][lower.T_CP]) == (n.cout + 31) // 32 * 32 and int(low.ops[0][lower.W_STRIDE]) == n.stride
 
 
 @pytest.mark.parametrize("key", sorted(ep.POOL_KEYS.values()))
@@ -331,7 +331,7 @@ def test_pool_probe_faults(key):
     probe, ref, raw, _ = _probed(key)
     pool = probe.net.nodes[-1]
     low = lower.lower(probe.net, probe.P)
-    assert [int(r[0]) for r in low.ops] == [lower.OP_STEM, lower.OP_MAXPOOL]
+    assert [int(r[lower.W_TYPE]) for r in low.ops] == [lower.OP_STEM, lower.OP_MAXPOOL]
     H, W = ref["s"].shape[1:3]
     Ho, Wo = ref["pool"].shape[1:3]
     assert (Ho, Wo) == ((H - 1) // 2 + 1, (W - 1) // 2 + 1) and (ref["s"] < 0).mean() > 0.3

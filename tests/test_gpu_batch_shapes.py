@@ -21,6 +21,7 @@ import pytest
 
 from oracle import align, nets as onets
 from scrfd_arcface_facerecognition_amd import archs
+from scrfd_arcface_facerecognition_amd.lower import W_X_SCOP
 
 from family_helpers import SlotGuard, force_family, forced_ran, own_data_tensors, slot_table, stack
 
@@ -380,13 +381,13 @@ def test_architecture_sub_batches(ctx, monkeypatch, arch, n, subs):
     P = archs.synth_params(net, seed=0)
     images = np.random.default_rng(17).integers(0, 256, (n,) + tuple(net.in_hw) + (3,), dtype=np.uint8)
     A = CompiledNet(ctx, net, P, max_batch=n)
-    kinds = {int(r[0]) for r in A.low.ops}
+    kinds = {int(r[lower.W_TYPE]) for r in A.low.ops}
     want = {"scrfd_10g": {lower.OP_STEMFUSED, lower.OP_BBLOCK, lower.OP_LATFPN}, "scrfd_500m": {lower.OP_STEM, lower.OP_DWCONV, lower.OP_MBBLOCK},
             "scrfd_500m+dwpw": {lower.OP_STEM, lower.OP_DWPW}, "arcface_r50": {lower.OP_STEMBLOCK, lower.OP_BBLOCK},
             "arcface_mbf": {lower.OP_MBBLOCK}}[arch]
     assert want <= kinds, (arch, kinds)
     if det:                                                  # the three fused detector heads (sigmoid on the class scores, fp32 output)
-        assert sum(1 for r in A.low.ops if int(r[0]) == lower.OP_CONV and r[12] > 0) == 3
+        assert sum(1 for r in A.low.ops if int(r[lower.W_TYPE]) == lower.OP_CONV and r[lower.W_NSIG] > 0) == 3
     try:
         oracle = _heads_oracle(net, P, images) if det else _embedding_oracle(net, P, images, components=(name == "arcface_r50"))
         A.run(images)
@@ -418,7 +419,7 @@ def test_profiled_run_equals_plain_run(ctx, monkeypatch, arch, n):
             assert np.array_equal(raw(cn, k, 0, n), plain[k]), k
         assert ms.shape == (len(cn.low.op_names),) and np.isfinite(ms).all()
         # an op that launches nothing has no time of its own: a block's shortcut conv absorbed by its consumer's generation-12 pick
-        absorbed = {int(cn.low.ops[p["op"]][31]) - 1 for p in cn.plans() if p["batch"] == n and p["gen"] == 12}
+        absorbed = {int(cn.low.ops[p["op"]][W_X_SCOP]) - 1 for p in cn.plans() if p["batch"] == n and p["gen"] == 12}
         for oi, t in enumerate(ms):
             assert t >= 0.0 if oi in absorbed else t > 0.0, (oi, cn.low.op_names[oi], float(t))
     finally:

@@ -52,7 +52,7 @@ def test_random_bottleneck(ctx, seed):
     net.add(Conv("b.pw2", "b.dw", g, cout, k=1, pad=0, act=acts[2], res="x" if res else None))
     net.outputs = ["b.pw2"]
     P = archs.synth_params(net, seed=seed)
-    fused = sum(int(r[0]) == 8 for r in lower.lower(net, P).ops)
+    fused = sum(int(r[lower.W_TYPE]) == lower.OP_MBBLOCK for r in lower.lower(net, P).ops)
     images = rng.integers(0, 256, (batch,) + hw + (3,), dtype=np.uint8)
     err = run(ctx, net, P, images, "b.pw2")
     # fused exactly when the 9 x 9 input region and both expanded maps fit LDS (csrc/mbf_block.hip mbf_lds_bytes)

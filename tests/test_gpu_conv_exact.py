@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import exact_probe as ep
+from scrfd_arcface_facerecognition_amd.lower import OP_CONV, W_TYPE, W_X_DST2
 from family_helpers import FAMILIES, force_family, forced_ran, own_data_tensors
 
 pytestmark = pytest.mark.gpu
@@ -112,7 +113,7 @@ def _family_bn(ctx, monkeypatch, code, shape):
         force_family(monkeypatch, code)
 
         def low_ok(low):
-            flags = {nm: (int(r[0]), int(r[11]) & lower.CF_BORDER) for nm, r in zip(low.op_names, low.ops)}
+            flags = {nm: (int(r[lower.W_TYPE]), int(r[lower.W_FLAGS]) & lower.CF_BORDER) for nm, r in zip(low.op_names, low.ops)}
             assert flags["c"] == (lower.OP_CONV, lower.CF_BORDER) and flags["r"] == (lower.OP_CONV, lower.CF_BORDER), low.op_names
         ran = run_probe(ctx, ep.FAMILY_BN_KEYS[shape], code, check_low=low_ok)       # equality first, whichever variant took the layers
         BN_RAN[(code, shape)] = sorted(set(ran) & {"c", "r"})
@@ -147,7 +148,7 @@ def test_every_family_ran_a_border_class_conv(ctx, monkeypatch):
 # ---- fused ops: fused and unfused lowering, each exact against the reference and hence against each other --------------------------------
 
 def _kinds(low):
-    return [int(r[0]) for r in low.ops]
+    return [int(r[W_TYPE]) for r in low.ops]
 
 
 def _env(monkeypatch, probe_key, **kv):
@@ -183,7 +184,7 @@ def test_fused_ir_block_exact(ctx, monkeypatch, fuse, shape):
     def low_ok(low):
         assert (_kinds(low).count(lower.OP_BBLOCK) == 1) == bool(fuse) and (len(low.ops) == 2) == bool(fuse), low.op_names
         op = low.ops[low.op_names.index("b.conv2" if fuse else "b.conv1")]
-        assert int(op[0]) == (lower.OP_BBLOCK if fuse else lower.OP_CONV) and int(op[11]) & lower.CF_BORDER, low.op_names
+        assert int(op[lower.W_TYPE]) == (lower.OP_BBLOCK if fuse else lower.OP_CONV) and int(op[lower.W_FLAGS]) & lower.CF_BORDER, low.op_names
     run_probe(ctx, key, check_low=low_ok)
 
 
@@ -237,7 +238,7 @@ def test_fused_stem_block_exact(ctx, monkeypatch, fuse, shape):
     _env(monkeypatch, key, FID_NO_STEMBLOCK_FUSE=None if fuse else "1")
 
     def low_ok(low):
-        assert (int(low.ops[0][0]) == lower.OP_STEMBLOCK) == fuse and ("stem.even" in low.tensor_id) == fuse and ("stem" in low.tensor_id) != fuse
+        assert (int(low.ops[0][lower.W_TYPE]) == lower.OP_STEMBLOCK) == fuse and ("stem.even" in low.tensor_id) == fuse and ("stem" in low.tensor_id) != fuse
     run_probe(ctx, key, check_low=low_ok)
 
 
@@ -250,9 +251,9 @@ def test_fused_stem_block_bn_exact(ctx, monkeypatch, fuse, shape):
     _env(monkeypatch, key, FID_NO_STEMBLOCK_FUSE=None if fuse else "1")
 
     def low_ok(low):
-        assert (int(low.ops[0][0]) == lower.OP_STEMBLOCK) == fuse and ("stem.even" in low.tensor_id) == fuse and ("stem" in low.tensor_id) != fuse
+        assert (int(low.ops[0][lower.W_TYPE]) == lower.OP_STEMBLOCK) == fuse and ("stem.even" in low.tensor_id) == fuse and ("stem" in low.tensor_id) != fuse
         op = low.ops[low.op_names.index("b.conv1")]
-        assert int(op[0]) == (lower.OP_STEMBLOCK if fuse else lower.OP_CONV) and int(op[11]) & lower.CF_BORDER, low.op_names
+        assert int(op[lower.W_TYPE]) == (lower.OP_STEMBLOCK if fuse else lower.OP_CONV) and int(op[lower.W_FLAGS]) & lower.CF_BORDER, low.op_names
     run_probe(ctx, key, check_low=low_ok)
 
 
@@ -264,7 +265,7 @@ def test_fused_shortcut_stride2_exact(ctx, monkeypatch, fuse, shape):
     _env(monkeypatch, key, FID_NO_DOWN_FUSE=None if fuse else "1")
 
     def low_ok(low):
-        assert (len(low.ops) == 2) == fuse and any(int(r[20]) > 0 for r in low.ops if int(r[0]) == 2) == fuse, low.op_names
+        assert (len(low.ops) == 2) == fuse and any(int(r[W_X_DST2]) > 0 for r in low.ops if int(r[W_TYPE]) == OP_CONV) == fuse, low.op_names
     run_probe(ctx, key, check_low=low_ok)
 
 
@@ -295,8 +296,8 @@ def _shortcut_case(ctx, monkeypatch, key, mode, border):
     ref, _ = ep.cached_reference(key)
     cn = CompiledNet(ctx, probe.net, probe.P, max_batch=probe.batch)
     try:
-        assert (sum(int(r[0]) == 2 and int(r[23]) > 0 for r in cn.low.ops) == 1) == (mode != "plain")
-        assert bool(int(cn.low.ops[cn.low.op_names.index("b.conv1")][11]) & lower.CF_BORDER) == border
+        assert (sum(int(r[lower.W_TYPE]) == lower.OP_CONV and int(r[lower.W_X_SRC2]) > 0 for r in cn.low.ops) == 1) == (mode != "plain")
+        assert bool(int(cn.low.ops[cn.low.op_names.index("b.conv1")][lower.W_FLAGS]) & lower.CF_BORDER) == border
         names = [nm for nm in probe.net.outputs if nm in own_data_tensors(cn.low)]
         assert names == probe.net.outputs
         got = []

@@ -191,7 +191,7 @@ def test_fused_shortcut_stride2(ctx, monkeypatch, fuse, hw, planes, batch):
     net.outputs = ["b.conv2"]
     P = archs.synth_params(net, seed=21)
     low = lower.lower(net, P)
-    assert (len(low.ops) == 3) == fuse and any(int(r[20]) > 0 for r in low.ops if int(r[0]) == 2) == fuse
+    assert (len(low.ops) == 3) == fuse and any(int(r[lower.W_X_DST2]) > 0 for r in low.ops if int(r[lower.W_TYPE]) == lower.OP_CONV) == fuse
     images = np.random.default_rng(8).integers(0, 256, (batch,) + hw + (3,), dtype=np.uint8)
     cn = CompiledNet(ctx, net, P, max_batch=batch)
     cn.run(images)
@@ -235,7 +235,7 @@ def test_fused_basic_block(ctx, monkeypatch, fuse, hw, planes, batch, act2):
     net.outputs = ["b1.conv2"]
     P = archs.synth_params(net, seed=23)
     low = lower.lower(net, P)
-    assert (len(low.ops) == 3) == fuse and (sum(int(r[0]) == 6 for r in low.ops) == 2) == fuse
+    assert (len(low.ops) == 3) == fuse and (sum(int(r[lower.W_TYPE]) == lower.OP_BBLOCK for r in low.ops) == 2) == fuse
     images = np.random.default_rng(9).integers(0, 256, (batch,) + hw + (3,), dtype=np.uint8)
     cn = CompiledNet(ctx, net, P, max_batch=batch)
     cn.run(images)
@@ -280,7 +280,7 @@ def test_fused_depthwise_pointwise(ctx, monkeypatch, fuse, hw, groups, cout, str
     net.outputs = ["pw"]
     P = archs.synth_params(net, seed=31)
     low = lower.lower(net, P)
-    assert (sum(int(r[0]) == 7 for r in low.ops) == 1) == fuse and (sum(int(r[0]) == 4 for r in low.ops) == 0) == fuse
+    assert (sum(int(r[lower.W_TYPE]) == lower.OP_DWPW for r in low.ops) == 1) == fuse and (sum(int(r[lower.W_TYPE]) == lower.OP_DWCONV for r in low.ops) == 0) == fuse
     images = np.random.default_rng(10).integers(0, 256, (batch,) + hw + (3,), dtype=np.uint8)
     cn = CompiledNet(ctx, net, P, max_batch=batch)
     cn.run(images)
@@ -318,7 +318,7 @@ def test_fused_bottleneck(ctx, monkeypatch, fuse, hw, cin, g, cout, stride, res,
     net.outputs = ["b.pw2"]
     P = archs.synth_params(net, seed=51)
     low = lower.lower(net, P)
-    assert (sum(int(r[0]) == 8 for r in low.ops) == 1) == fuse and (sum(int(r[0]) == 4 for r in low.ops) == 0) == fuse
+    assert (sum(int(r[lower.W_TYPE]) == lower.OP_MBBLOCK for r in low.ops) == 1) == fuse and (sum(int(r[lower.W_TYPE]) == lower.OP_DWCONV for r in low.ops) == 0) == fuse
     images = np.random.default_rng(12).integers(0, 256, (batch,) + hw + (3,), dtype=np.uint8)
     cn = CompiledNet(ctx, net, P, max_batch=batch)
     cn.run(images)
@@ -362,7 +362,7 @@ def test_fused_shortcut_conv(ctx, monkeypatch, mode, hw, cin, cout, batch):
     net.outputs = ["b.conv2"]
     P = archs.synth_params(net, seed=61)
     low = lower.lower(net, P)
-    assert (sum(int(r[0]) == 2 and int(r[23]) > 0 for r in low.ops) == 1) == (mode != "plain") and "b.down" in low.op_names
+    assert (sum(int(r[lower.W_TYPE]) == lower.OP_CONV and int(r[lower.W_X_SRC2]) > 0 for r in low.ops) == 1) == (mode != "plain") and "b.down" in low.op_names
     images = np.random.default_rng(14).integers(0, 256, (batch,) + hw + (3,), dtype=np.uint8)
     cn = CompiledNet(ctx, net, P, max_batch=batch)
     for _ in range(3):                                      # the first run tunes (the shortcut op runs); later runs skip it when conv2's pick is generation 12
@@ -406,7 +406,7 @@ def test_fused_stem_block(ctx, monkeypatch, fuse, hw, pre_bn, act, block, batch)
     net.outputs = outs
     P = archs.synth_params(net, seed=71)
     low = lower.lower(net, P)
-    assert (int(low.ops[0][0]) == lower.OP_STEMBLOCK) == fuse
+    assert (int(low.ops[0][lower.W_TYPE]) == lower.OP_STEMBLOCK) == fuse
     if fuse:
         assert ("stem.even" in low.tensor_id) == block and "stem" not in low.tensor_id
     images = np.random.default_rng(15).integers(0, 256, (batch,) + hw + (3,), dtype=np.uint8)
@@ -454,7 +454,7 @@ def test_fused_lateral_fpn(ctx, monkeypatch, fuse, hw, cch, batch):
     net.outputs = ["fpn0", "fpn1", "fpn2"]
     P = archs.synth_params(net, seed=81)
     low = lower.lower(net, P)
-    n_fused = sum(int(r[0]) == lower.OP_LATFPN for r in low.ops)
+    n_fused = sum(int(r[lower.W_TYPE]) == lower.OP_LATFPN for r in low.ops)
     assert n_fused == (3 if fuse else 0), low.op_names
     if fuse:
         assert "lat0" not in low.tensor_id and "lat1" in low.tensor_id and "lat2" in low.tensor_id     # only the laterals a finer level adds are stored

@@ -137,9 +137,9 @@ def test_arcface_mbf_embeddings(ctx, monkeypatch, fusion, table):
         monkeypatch.setenv("FID_DWPW_FUSE", "1")
     net = archs.ARCHS[table]()
     P = archs.synth_params(net, seed=0)
-    kinds = [int(r[0]) for r in lower.lower(net, P).ops]
+    kinds = [int(r[lower.W_TYPE]) for r in lower.lower(net, P).ops]
     nb, ndw = (29, 29) if table == "arcface_mbf" else (15, 16)
-    assert (kinds.count(8), kinds.count(7)) == {"bottleneck": (nb, 0), "dwpw": (0, ndw), "none": (0, 0)}[fusion]
+    assert (kinds.count(lower.OP_MBBLOCK), kinds.count(lower.OP_DWPW)) == {"bottleneck": (nb, 0), "dwpw": (0, ndw), "none": (0, 0)}[fusion]
     images = np.random.default_rng(12).integers(0, 256, (2, 112, 112, 3), dtype=np.uint8)
     got, ref = run_both(ctx, net, P, images, ["fc"])
     e, r = got["fc"].reshape(2, 512), ref["fc"].reshape(2, 512)
@@ -301,7 +301,10 @@ def test_truncated_blob_is_refused(ctx, arch, hw, monkeypatch):
     import ctypes as C
     from scrfd_arcface_facerecognition_amd import _lib
     from scrfd_arcface_facerecognition_amd._lib import FaceIdError, check
-    from scrfd_arcface_facerecognition_amd.lower import (OP_BBLOCK, OP_CONV, OP_DWPW, OP_LATFPN, OP_MBBLOCK, OP_STEMBLOCK, OP_STEMFUSED, lower)
+    from scrfd_arcface_facerecognition_amd.lower import (OP_BBLOCK, OP_CONV, OP_DWPW, OP_LATFPN, OP_MBBLOCK, OP_STEMBLOCK, OP_STEMFUSED, T_CP, W_B_B1, W_B_B2,
+                                                         W_B_S1, W_B_W1, W_B_W2, W_BOFF, W_D_BOFF, W_D_SOFF, W_D_WOFF, W_F_B0, W_F_B1, W_F_B2, W_F_W0, W_F_W1,
+                                                         W_F_W2, W_L_B0, W_L_W0, W_M_B1, W_M_DW, W_M_DWB, W_M_DWS, W_M_S1, W_M_W1, W_S_B1, W_S_S1, W_S_W1,
+                                                         W_SOFF, W_SRC, W_TYPE, W_WOFF, W_X_B2OFF, W_X_SRC2, W_X_W2OFF, lower)
     if arch == "scrfd_500m":
         monkeypatch.setenv("FID_DWPW_FUSE", "1")             # so that the table holds OP_DWPW records too
     net = archs.ARCHS[arch](hw)
@@ -316,31 +319,32 @@ def test_truncated_blob_is_refused(ctx, arch, hw, monkeypatch):
         return h
     h = create(len(low.blob))                                # the complete blob is accepted
     check(ctx.lib.fid_net_destroy(ctx.handle, h))
-    words = {OP_STEMFUSED: (20, 21, 22, 23, 24, 25), OP_BBLOCK: (20, 21, 22, 23, 24), OP_DWPW: (20, 21, 22), OP_MBBLOCK: (20, 21, 22, 24, 25, 28),
-             OP_STEMBLOCK: (20, 21, 22), OP_LATFPN: (20, 21)}      # (round 4's fused ops: W_S_W1 / B1 / S1, W_L_W0 / B0 -- ADVICE r4)
+    words = {OP_STEMFUSED: (W_F_W0, W_F_B0, W_F_W1, W_F_B1, W_F_W2, W_F_B2), OP_BBLOCK: (W_B_W1, W_B_B1, W_B_W2, W_B_B2, W_B_S1),
+             OP_DWPW: (W_D_WOFF, W_D_BOFF, W_D_SOFF), OP_MBBLOCK: (W_M_W1, W_M_B1, W_M_S1, W_M_DW, W_M_DWB, W_M_DWS),
+             OP_STEMBLOCK: (W_S_W1, W_S_B1, W_S_S1), OP_LATFPN: (W_L_W0, W_L_B0)}      # (round 4's fused ops: W_S_W1 / B1 / S1, W_L_W0 / B0 -- ADVICE r4)
     cuts, kinds = set(), set()
     for op in ops:
-        t = int(op[0])
-        ws = (13, 15, 16) + words.get(t, ()) + ((29, 30) if t == OP_CONV and op[23] > 0 else ())
+        t = int(op[W_TYPE])
+        ws = (W_WOFF, W_BOFF, W_SOFF) + words.get(t, ()) + ((W_X_W2OFF, W_X_B2OFF) if t == OP_CONV and op[W_X_SRC2] > 0 else ())
         for w in ws:
             if op[w] > 0:
                 cuts.add(int(op[w])); kinds.add((t, w))
     assert len(cuts) > 10
     if arch == "arcface_r50":
-        assert (OP_CONV, 29) in kinds and (OP_BBLOCK, 22) in kinds
-        assert (OP_STEMBLOCK, 20) in kinds and (OP_STEMBLOCK, 21) in kinds
+        assert (OP_CONV, W_X_W2OFF) in kinds and (OP_BBLOCK, W_B_W2) in kinds
+        assert (OP_STEMBLOCK, W_S_W1) in kinds and (OP_STEMBLOCK, W_S_B1) in kinds
     if arch == "scrfd_10g":
-        assert (OP_LATFPN, 20) in kinds and (OP_LATFPN, 21) in kinds
+        assert (OP_LATFPN, W_L_W0) in kinds and (OP_LATFPN, W_L_B0) in kinds
     if arch == "arcface_mbf":
-        assert (OP_MBBLOCK, 20) in kinds and (OP_MBBLOCK, 28) in kinds
+        assert (OP_MBBLOCK, W_M_W1) in kinds and (OP_MBBLOCK, W_M_DWS) in kinds
     if arch == "scrfd_500m":
-        assert (OP_DWPW, 20) in kinds
+        assert (OP_DWPW, W_D_WOFF) in kinds
     for cut in sorted(cuts):
         with pytest.raises(FaceIdError):
             create(cut)
     # the two-chunk image of a 64-channel fused block: a blob that holds only its FIRST chunk (the 73 728 bytes round 3 checked) is refused
     for op in ops:
-        if int(op[0]) == OP_BBLOCK and int(tens[op[1]][1]) == 64:
+        if int(op[W_TYPE]) == OP_BBLOCK and int(tens[op[W_SRC]][T_CP]) == 64:
             with pytest.raises(FaceIdError):
-                create(max(int(op[20]), int(op[22])) + 73728)
+                create(max(int(op[W_B_W1]), int(op[W_B_W2])) + 73728)
             break

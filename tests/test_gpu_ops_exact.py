@@ -27,6 +27,7 @@ import sys
 import pytest
 
 import exact_probe as ep
+from scrfd_arcface_facerecognition_amd.lower import OP_CONV, W_TYPE
 from test_gpu_conv_exact import _env, _kinds, run_probe
 
 pytestmark = pytest.mark.gpu
@@ -69,7 +70,7 @@ def _split_ok(low, batch, names, force, slabs, cus):
     """the mirror's slabs of every probed op of a case: more than one, and the ones the case is about"""
     out = {}
     for name in names:
-        assert int(low.ops[low.op_names.index(name)][0]) == 2, low.op_names
+        assert int(low.ops[low.op_names.index(name)][W_TYPE]) == OP_CONV, low.op_names
         m = ep.split_mirror(*ep.conv_geometry(low, name, batch), cus, _force(force))
         assert m["ksplit"] > 1 and len(m["slabs"]) > 1 and (slabs is None or m["slabs"] == slabs), (name, m)
         out[name] = m

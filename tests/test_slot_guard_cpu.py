@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from scrfd_arcface_facerecognition_amd import archs
-from scrfd_arcface_facerecognition_amd.lower import lower
+from scrfd_arcface_facerecognition_amd.lower import T_SLOT, lower
 
 from family_helpers import guard_regions, own_data_tensors, slot_table, stack
 
@@ -58,7 +58,7 @@ def test_view_reports_the_slot_of_its_base(name):
         fc = next(x for x in net.nodes if x.name == v[:-len(".in_view")])
         vi, bi = low.tensor_id[v], low.tensor_id[fc.src]
         assert t_slot[vi] == t_slot[bi] and t_bytes[vi] == t_bytes[bi]
-        assert int(low.tensors[vi][5]) == int(low.tensors[bi][5]) >= 0
+        assert int(low.tensors[vi][T_SLOT]) == int(low.tensors[bi][T_SLOT]) >= 0
 
 
 @pytest.mark.parametrize("name", sorted(NETS))

@@ -59,7 +59,7 @@ def main():
     pretty = dict(zip(names, (normalise(d) for d in dem)))
     from bench import node_macs
     from scrfd_arcface_facerecognition_amd import archs
-    from scrfd_arcface_facerecognition_amd.lower import lower
+    from scrfd_arcface_facerecognition_amd.lower import OP_CONV, W_TYPE, W_X_SRC2, W_X_W2OFF, lower
     net = archs.ARCHS[arch]()
     low = lower(net, archs.synth_params(net, 0))
     by_name = {nd.name: nd for nd in net.nodes}
@@ -68,7 +68,7 @@ def main():
         gf = 2.0 * sum(node_macs(net, by_name[nm]) for nm in nodes) * batch / 1e9
         ks = op_kernels.get(oi)
         if not ks:
-            if int(low.ops[oi, 0]) == 2 and int(low.ops[oi, 23]) == 0 and int(low.ops[oi, 29]) > 0:
+            if int(low.ops[oi, W_TYPE]) == OP_CONV and int(low.ops[oi, W_X_SRC2]) == 0 and int(low.ops[oi, W_X_W2OFF]) > 0:
                 carry += gf                                  # a shortcut conv its consumer absorbed: computed by the consumer's kernel
             else:
                 unmapped += gf
@@ -77,7 +77,7 @@ def main():
         out[k] = out.get(k, 0.0) + gf
     if carry:
         # absorbed shortcuts ride in the stride-2 convs (generation 12): spread over the kernels of the ops that name a second weight image
-        hosts = [pretty[op_kernels[oi][0]] for oi in op_kernels if int(low.ops[oi, 0]) == 2 and int(low.ops[oi, 23]) > 0]
+        hosts = [pretty[op_kernels[oi][0]] for oi in op_kernels if int(low.ops[oi, W_TYPE]) == OP_CONV and int(low.ops[oi, W_X_SRC2]) > 0]
         for h in hosts:
             out[h] = out.get(h, 0.0) + carry / len(hosts)
     print(json.dumps({"arch": arch, "batch": batch, "gflop_per_run_by_kernel": {k: round(v, 3) for k, v in sorted(out.items())},

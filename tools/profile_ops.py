@@ -11,6 +11,7 @@ from bench import node_macs  # noqa: E402
 from scrfd_arcface_facerecognition_amd import archs  # noqa: E402
 from scrfd_arcface_facerecognition_amd._lib import Context  # noqa: E402
 from scrfd_arcface_facerecognition_amd.engine import CompiledNet  # noqa: E402
+from scrfd_arcface_facerecognition_amd.lower import W_TYPE  # noqa: E402
 
 arch = sys.argv[1] if len(sys.argv) > 1 else "arcface_r50"
 batch = int(sys.argv[2]) if len(sys.argv) > 2 else 64
@@ -28,7 +29,7 @@ by_name = {nd.name: nd for nd in net.nodes}
 print(f"{arch} batch {batch}: total {best.sum():.3f} ms")
 print(f"{'op':28s} {'type':4s} {'out CxHxW':>14s} {'k':>2s} {'s':>2s} {'GFLOP':>8s} {'us':>8s} {'TFLOP/s':>8s}")
 for oi, names in enumerate(cn.low.op_nodes):
-    t = int(cn.low.ops[oi, 0])
+    t = int(cn.low.ops[oi, W_TYPE])
     fl = 2.0 * sum(node_macs(net, by_name[nm]) for nm in names) * batch
     node = by_name[names[-1]]
     c, h, w = shp[node.name]
