@@ -316,6 +316,71 @@ int fid_track_identify(fid_ctx *ctx, fid_tracker *trk, const int32_t *counts_dev
                        const int32_t *track_dev, const int32_t *offsets_dev, const int32_t *src_dev, int row_cap, const int32_t *idx_dev,
                        const float *score_dev, int n_rows, int32_t *ident_idx_dev, float *ident_score_dev);
 
+/* ---- drawing detections, names and scores onto the frames (reference main.py:130-148 with utils/helpers.py:126-179 draw_bbox / draw_bbox_info):
+ * the overlay of a whole batch in place on the device, enqueued behind the match with nothing read back first.  OpenCV's thick-line caps and
+ * Hershey font are NOT reproduced; taken from the reference are the integer truncation of the box, the corner length, the
+ * bar rectangle, the text anchor, the label string and its two decimals, the unknown colour and the draw order.  The raster rules:
+ *
+ * One face, from its det row (x1f, y1f, x2f, y2f, conf), an identity (idx, score), an optional track id, the label table and the style:
+ *   x1, y1, x2, y2 = the floats truncated toward zero; w = x2 - x1, h = y2 - y1.  The face draws nothing unless all four floats are finite,
+ *   each |v| < 2^23, and w > 0 && h > 0.  Known = 0 <= idx < G with a label table: the colour is the table's BGR, else style.unknown_bgr.
+ *   L = (int)(proportion * (double)min(w, h));  r = (thickness - 1) / 2;  s = score if finite and > 0, else 0;
+ *   bh = (int)(s * (float)h) in fp32;  cents = min((int)rint((double)s * 100.0), 999) (ties to even: Python's f"{np.float32(s):.2f}").
+ *   Text of a known face: "#<id> " (only with FID_DRAW_TRACK_ID and a track id >= 0), the name (at most FID_LABEL_MAX bytes, a byte outside
+ *   0x20..0x7E drawn as '?'), ": ", cents / 100, '.', two digits.  Of an unknown face: "#<id>" under the same condition, else none.
+ *   Pixel set, clipped to the frame, all in the face's colour:
+ *     outline   x1 <= x <= x2 on rows y1 and y2, y1 <= y <= y2 on columns x1 and x2;
+ *     arms      per corner (cx, cy, sx, sy) the segments cx .. cx + sx * L on row cy and cy .. cy + sy * L on column cx, inclusive, every point
+ *               of a segment stamping a thickness x thickness square;
+ *     bar       (known faces, style.bar) x2 + 10 <= x <= x2 + 20, y2 - bh <= y <= y2;
+ *     text      (style.text_scale = t > 0) character k has its left edge at X = x1 + 6 * t * k and the bottom row of its cell at Y = y1 - 10; the
+ *               5 x 7 glyph (fid_draw_glyphs: 95 x 7 bytes for ASCII 0x20..0x7E, top row first, bit 4 = leftmost column) is magnified t
+ *               times: (x, y) is lit iff the glyph bit at column (x - X) / t, row 6 - (Y - y) / t is set.
+ * One frame: a pixel takes the colour of the HIGHEST face index whose set contains it (the reference draws the faces in detection order); a
+ * pixel in no set is not written, and nothing is ever read from the frame.
+ *
+ * fid_labels: per gallery row the name bytes and a BGR colour, device resident.  names: the rows' bytes back to back, row g =
+ * names[name_offsets[g] .. name_offsets[g+1]); bgr [G,3] or NULL: row g gets h = (uint32_t)(g + 1) * 2654435761u -> (h >> 24, (h >> 16) & 255,
+ * (h >> 8) & 255) (the reference picks them at random, main.py:160).  fid_labels_create synchronises (one copy); G <= 0 or offsets that
+ * decrease are FID_E_INVALID.
+ *
+ * fid_draw_faces: frames_dev uint8 [B,H,W,3] drawn IN PLACE (a caller that still needs the clean frames draws after their last reader);
+ * det_dev [B,cap,5] / counts_dev [B] as fid_scrfd_postprocess* writes them.  Three identity forms:
+ *   idx_dev == NULL      detections only: n_b = min(max(counts[b], 0), cap), every face unknown;
+ *   offsets_dev == NULL  slots: face (b, f) reads idx / score[b * id_stride + f], n_b = min(max(counts[b], 0), cap, id_stride) (a pipeline's
+ *                        B x F slots: id_stride = F; fid_track_identify's ident_idx / ident_score: id_stride = cap);
+ *   offsets_dev != NULL  rows in fid_face_pack's format: face f of frame b is row offsets[b] + f,
+ *                        n_b = clamp(min(offsets[b+1], n_rows) - offsets[b], 0, cap) (a negative offsets[b]: no face).
+ * track_dev: optional int32 [B,cap,2] as fid_track_step writes it (word 0 is the id).  labels may be NULL: no names, every face unknown.
+ * FID_E_INVALID, nothing enqueued, the frames untouched: a NULL ctx, frames, det, counts or style; B, H, W or cap <= 0; B * cap or H * W * 3
+ * not fitting int32; thickness even or outside 1 .. 15; text_scale outside 0 .. 4; proportion NaN or outside [0, 1]; idx without score;
+ * id_stride <= 0 in the slot form; n_rows < 0.  Asynchronous on the context's stream; it never synchronises with the host, except once when
+ * B * cap outgrows the context's scratch.
+ *
+ * fid_draw_faces_host: the same records and the same coverage test in plain loops on HOST arrays, no device involved: the definition the
+ * device kernels are tested against, and what utils/helpers.draw_bbox / draw_bbox_info / draw_faces call.  The label table is given as the
+ * arguments of fid_labels_create (name_offsets NULL: none). */
+typedef struct fid_labels fid_labels;
+typedef struct fid_draw_style {
+    double proportion;             /* corner length / min(w, h), [0, 1]; a double: the reference multiplies by the Python float 0.2 */
+    int32_t thickness;             /* of the corner arms: odd, 1 .. 15 */
+    int32_t text_scale;            /* 0: no text; 1 .. 4 */
+    int32_t bar;                   /* non-zero: the similarity bar of known faces */
+    int32_t flags;                 /* FID_DRAW_TRACK_ID */
+    uint8_t unknown_bgr[4];        /* colour of an unknown face (byte 3 unused) */
+} fid_draw_style;
+#define FID_LABEL_MAX 32
+#define FID_DRAW_TRACK_ID 1
+int fid_labels_create(fid_ctx *ctx, const char *names, const int32_t *name_offsets, const uint8_t *bgr, int G, fid_labels **out);
+int fid_labels_destroy(fid_ctx *ctx, fid_labels *labels);
+int fid_draw_faces(fid_ctx *ctx, uint8_t *frames_dev, int B, int H, int W, const float *det_dev, const int32_t *counts_dev, int cap,
+                   const int32_t *idx_dev, const float *score_dev, int id_stride, const int32_t *offsets_dev, int n_rows,
+                   const int32_t *track_dev, fid_labels *labels, const fid_draw_style *style);
+int fid_draw_faces_host(uint8_t *frames, int B, int H, int W, const float *det, const int32_t *counts, int cap, const int32_t *idx,
+                        const float *score, int id_stride, const int32_t *offsets, int n_rows, const int32_t *track, const char *names,
+                        const int32_t *name_offsets, const uint8_t *bgr, int G, const fid_draw_style *style);
+int fid_draw_glyphs(uint8_t *out /* [95 * 7] */);
+
 /* ---- face gates of the reference's product layer: replaces smart_face_recognition.py:1145-1216
  * (assess_face_quality), :1218-1297 (get_face_pose_angles / is_side_face), :1299-1399 (analyze_bbox_for_side_face) and the
  * best-face selection with its four rejections (:1473-1519), for every face of a batch in one launch on the post-process's own

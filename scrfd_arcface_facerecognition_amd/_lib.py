@@ -84,7 +84,44 @@ class TrackConfig(C.Structure):
 TRACK_SLOT_WORDS = 10            # FID_TRACK_SLOT_WORDS
 TRACK_STARTED, TRACK_EMBED = 1 << 8, 1 << 9
 
+FID_LABEL_MAX = 32               # name bytes a label shows
+DRAW_TRACK_ID = 1                # FID_DRAW_TRACK_ID
+
+
+class DrawStyle(C.Structure):
+    """fid_draw_style (include/faceid.h): corner length as a fraction of min(w, h) (a double, like the reference's Python float), thickness
+    of the corner arms (odd, 1 .. 15), text scale (0 = no text, 1 .. 4), similarity bar on / off, flags (DRAW_TRACK_ID), colour of an unknown
+    face; the defaults are the reference's (draw_bbox's 0.2 and 3, main.py:148's (255, 0, 0))"""
+    _fields_ = [("proportion", C.c_double), ("thickness", C.c_int32), ("text_scale", C.c_int32), ("bar", C.c_int32), ("flags", C.c_int32),
+                ("unknown_bgr", C.c_uint8 * 4)]
+
+    def __init__(self, proportion=0.2, thickness=3, text_scale=2, bar=1, flags=0, unknown_bgr=(255, 0, 0)):
+        super().__init__()
+        self.proportion, self.thickness, self.text_scale = float(proportion), int(thickness), int(text_scale)
+        self.bar, self.flags = int(bar), int(flags)
+        self.unknown_bgr[:3] = [int(v) for v in unknown_bgr]
+
+
+def label_arrays(names, colors=None):
+    """names (str or bytes per gallery row), colors (BGR triple per row, or None) as fid_labels_create / fid_draw_faces_host take them:
+    (name bytes, int32 [G+1] offsets, uint8 [G,3] or None).  A str is encoded as UTF-8; the table keeps FID_LABEL_MAX bytes of it."""
+    raw = [n if isinstance(n, (bytes, bytearray)) else str(n).encode("utf-8") for n in names]
+    offsets = np.zeros(len(raw) + 1, np.int32)
+    offsets[1:] = np.cumsum([len(r) for r in raw])
+    bgr = None
+    if colors is not None:
+        bgr = np.ascontiguousarray(np.asarray(colors).reshape(len(raw), 3), dtype=np.uint8)
+    return b"".join(bytes(r) for r in raw), offsets, bgr
+
+
 SIGNATURES = {
+    "fid_labels_create": (C.c_int, [C.c_void_p, C.c_char_p, c_i32_p, C.c_void_p, C.c_int, c_void_pp]),
+    "fid_labels_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fid_draw_faces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                 C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fid_draw_faces_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                      C.c_void_p, C.c_int, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "fid_draw_glyphs": (C.c_int, [C.c_void_p]),
     "fid_abi_version": (C.c_int, []),
     "fid_last_error": (C.c_char_p, []),
     "fid_device_count": (C.c_int, [c_int_p]),

@@ -266,9 +266,36 @@ class Gallery:
         check(self.ctx.lib.fid_match(self.ctx.handle, self.handle, _lib._ptr(q_f16_dev), int(n), float(thresh),
                                      _lib._ptr(idx_dev), _lib._ptr(score_dev)))
 
+    def labels(self) -> "LabelTable":
+        """the names of this gallery's rows as a device label table (default colours), built once"""
+        if getattr(self, "_labels", None) is None:
+            self._labels = LabelTable(self.ctx, self.names)
+        return self._labels
+
     def close(self):
+        if getattr(self, "_labels", None) is not None:
+            self._labels.close()
+            self._labels = None
         if self.handle:
             self.ctx.lib.fid_gallery_destroy(self.ctx.handle, self.handle)
+            self.handle = None
+
+
+class LabelTable:
+    """fid_labels: per gallery row the name the overlay prints (its first FID_LABEL_MAX bytes; UTF-8 for a str) and a BGR colour, device
+    resident -- what fid_draw_faces looks an identity up in.  colors: [G,3] BGR or None (a fixed colour per row index)."""
+
+    def __init__(self, ctx: Context, names: Sequence, colors=None):
+        self.ctx, self.G = ctx, len(names)
+        raw, offsets, bgr = _lib.label_arrays(names, colors)
+        h = C.c_void_p()
+        check(ctx.lib.fid_labels_create(ctx.handle, raw, offsets.ctypes.data_as(_lib.c_i32_p),
+                                        bgr.ctypes.data_as(C.c_void_p) if bgr is not None else None, self.G, C.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.fid_labels_destroy(self.ctx.handle, self.handle)
             self.handle = None
 
 

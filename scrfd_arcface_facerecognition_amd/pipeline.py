@@ -187,6 +187,29 @@ class FacePipeline:
         self.embed(frames_dev, H, W)
         self.match(gallery, thresh)
 
+    # -- overlay -----------------------------------------------------------------------------------
+    @staticmethod
+    def _label_handle(labels):
+        """a LabelTable, a Gallery (its cached table) or None (no names: every face is drawn as unknown)"""
+        if labels is None:
+            return None
+        if hasattr(labels, "labels"):
+            labels = labels.labels()
+        return labels.handle
+
+    def _draw(self, frames_dev, H, W, labels, style, idx, score, id_stride, offsets=None, n_rows=0, track=None):
+        style = style if style is not None else _lib.DrawStyle()
+        check(self.ctx.lib.fid_draw_faces(self.ctx.handle, _lib._ptr(frames_dev), self.B, int(H), int(W), C.c_void_p(self.post.det.ptr),
+                                          C.c_void_p(self.post.counts.ptr), self.post.cap, _lib._ptr(idx), _lib._ptr(score), int(id_stride),
+                                          _lib._ptr(offsets), int(n_rows), _lib._ptr(track), self._label_handle(labels), C.byref(style)))
+
+    def draw(self, frames_dev, H, W, labels, style=None):
+        """Draw the last step's boxes, names and scores onto frames_dev uint8 [B,H,W,3], in place and on the device (fid_draw_faces): what
+        frame_processor does with cv2 per face (main.py:132-148).  Enqueued behind the match; nothing is read back.  Call it after the
+        step's last reader of the clean frames (run_step), and before the buffer is handed back to an upload.
+        labels: a LabelTable, a Gallery, or None; style: _lib.DrawStyle (default: the reference's look)."""
+        self._draw(frames_dev, H, W, labels, style, self.idx, self.score, self.F)
+
     # -- results -----------------------------------------------------------------------------------
     def results(self, gallery: Gallery):
         """Host view of the last step: per frame a list of (bbox[4], det_score, kps[5,2], name, similarity)
@@ -275,6 +298,10 @@ class GroupedFacePipeline(FacePipeline):
         steps = self.embed_collected()
         if steps:
             self.match(gallery, thresh, n=steps * self.n_slots)
+
+    def draw(self, frames_dev, H, W, labels, style=None):
+        raise ValueError("GroupedFacePipeline.draw: a step's identities exist only when its group's last step has run, after its frames "
+                         "may have been overwritten; draw from results() on the host (utils.helpers.draw_faces)")
 
     def results(self, gallery: Gallery):
         """per step of the last finished group: the list FacePipeline.results returns for one batch"""
@@ -427,6 +454,10 @@ class PackedFacePipeline(FacePipeline):
                 FacePipeline.match(self, gallery, thresh, n=n)
         self.ctx.sync()
 
+    def draw(self, frames_dev, H, W, labels, style=None):
+        """FacePipeline.draw on the row table: face f of frame b is row offsets[b] + f; only the rows the last step ran carry an identity"""
+        self._draw(frames_dev, H, W, labels, style, self.idx, self.score, 0, offsets=self.offsets, n_rows=min(self.n_run, self.row_cap))
+
     # -- results -----------------------------------------------------------------------------------
     def _download(self):
         """host copies of the last step: counts [B], det [B,cap,5], kps [B,cap,10], idx [row_cap], score [row_cap]"""
@@ -561,6 +592,12 @@ class TrackedFacePipeline(PackedFacePipeline):
         """rows of the last step's table: the faces that went through the recogniser (reads 4 bytes back)"""
         total = int(self.ctx.borrow(self.offsets.ptr + 4 * self.B, (1,), np.int32).download()[0])
         return min(total, self.row_cap)
+
+    def draw(self, frames_dev, H, W, labels, style=None):
+        """FacePipeline.draw for EVERY detection, with its track's name and score; a style with the DRAW_TRACK_ID flag prints the track id"""
+        if not self._identified:
+            raise RuntimeError("TrackedFacePipeline: the last step has not been identified (match() / identify())")
+        self._draw(frames_dev, H, W, labels, style, self.ident_idx, self.ident_score, self.post.cap, track=self.track)
 
     # -- results -----------------------------------------------------------------------------------
     def results_tracked(self, gallery: Optional[Gallery] = None):

@@ -118,17 +118,70 @@ def match_gallery(embeddings, gallery, thresh, *, ctx=None, return_matrix=False)
     return out
 
 
-# ---- drawing (reference utils/helpers.py:126-179): visualisation only, needs OpenCV on the host ----
+# ---- drawing (reference utils/helpers.py:126-179): with OpenCV on the host, cv2's primitives; without it, the library's host rasteriser
+# (fid_draw_faces_host: the raster rules of include/faceid.h -- the same pixels fid_draw_faces writes on the device) ----
 def _cv2():
     try:
         import cv2
         return cv2
-    except ImportError as e:            # pragma: no cover
-        raise ImportError("draw_bbox / draw_bbox_info need opencv-python on the host") from e
+    except ImportError:
+        return None
+
+
+def _draw_host(image, boxes, idx=None, score=None, names=None, colors=None, track=None, style=None):
+    """fid_draw_faces_host on one uint8 [H,W,3] image in place: boxes [n,4], optional identities / label table / track ids"""
+    from .._lib import DrawStyle, label_arrays, load
+    if getattr(image, "dtype", None) != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+        raise ValueError(f"drawing needs a uint8 [H,W,3] image, not {getattr(image, 'dtype', None)} {getattr(image, 'shape', None)}")
+    n = len(boxes)
+    if n == 0:
+        return image
+    buf = image if image.flags.c_contiguous and image.flags.writeable else np.ascontiguousarray(image)
+    H, W = buf.shape[:2]
+    det = np.zeros((n, 5), np.float32)
+    det[:, :4] = np.asarray(boxes, dtype=np.float32).reshape(n, 4)
+    counts = np.array([n], np.int32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    idx = None if idx is None else np.ascontiguousarray(idx, np.int32)
+    score = None if score is None else np.ascontiguousarray(score, np.float32)
+    trk = None
+    if track is not None:
+        trk = np.zeros((n, 2), np.int32)
+        trk[:, 0] = track
+    raw, offsets, bgr = (None, None, None) if names is None else label_arrays(names, colors)
+    style = style if style is not None else DrawStyle()
+    check(load().fid_draw_faces_host(p(buf), 1, H, W, p(det), p(counts), n, p(idx), p(score), n, None, 0, p(trk), raw, p(offsets), p(bgr),
+                                     0 if names is None else len(names), C.byref(style)))
+    if buf is not image:
+        image[...] = buf
+    return image
+
+
+def draw_faces(image, faces, colors=None, style=None):
+    """Draw one frame's face list -- an entry of `results()` / `results_tracked()`: (bbox, det_score, kps, name, similarity[, track id, ...])
+    per face -- onto `image` (uint8 [H,W,3], in place; returned) on the host, in list order (a later face shows over an earlier one).
+    colors: {name: (b, g, r)} or None (a fixed colour per name, in order of first appearance); "Unknown" is drawn in style.unknown_bgr."""
+    names, idx = [], []
+    for face in faces:
+        name = face[3]
+        if name == "Unknown":
+            idx.append(-1)
+            continue
+        if name not in names:
+            names.append(name)
+        idx.append(names.index(name))
+    bgr = [colors[n] for n in names] if colors is not None and names else None
+    track = [face[5] for face in faces] if faces and all(len(face) > 5 for face in faces) else None
+    return _draw_host(image, [np.asarray(face[0], np.float32)[:4] for face in faces], idx, [face[4] for face in faces], names or None, bgr,
+                      track, style)
 
 
 def draw_bbox(image, bbox, color=(0, 255, 0), thickness=3, proportion=0.2):
     cv2 = _cv2()
+    if cv2 is None:
+        from .._lib import DrawStyle
+        return _draw_host(image, [np.asarray(bbox, np.float32)[:4]],
+                          style=DrawStyle(proportion, thickness, 0, 0, 0, tuple(int(c) for c in color[:3])))
     x1, y1, x2, y2 = map(int, bbox)
     cv2.rectangle(image, (x1, y1), (x2, y2), color, max(1, thickness // 3))
     L = int(min(x2 - x1, y2 - y1) * proportion)
@@ -140,6 +193,8 @@ def draw_bbox(image, bbox, color=(0, 255, 0), thickness=3, proportion=0.2):
 
 def draw_bbox_info(frame, bbox, similarity, name, color):
     cv2 = _cv2()
+    if cv2 is None:                     # name, two-decimal similarity, box and similarity bar in `color`
+        return _draw_host(frame, [np.asarray(bbox, np.float32)[:4]], [0], [similarity], [name], [tuple(int(c) for c in color[:3])])
     x1, y1, _, _ = map(int, bbox)
     cv2.putText(frame, f"{name}: {similarity:.2f}", (x1, y1 - 10), cv2.FONT_HERSHEY_SIMPLEX, 1, color, 2)
     draw_bbox(frame, bbox, color)

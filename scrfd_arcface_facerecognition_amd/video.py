@@ -34,10 +34,13 @@ class StreamRunner:
     per-frame face lists (FacePipeline.results) in frame order.  Upload of batch i+1 overlaps compute of batch i.
     An item of the iterable may also be a `(stream_id, frame)` pair -- several cameras in one iterable, each camera's frames in time
     order --: a TrackedFacePipeline keeps the cameras' tracks apart by it (a bare frame is camera 0) and is told which frames of a ragged
-    last batch are padding, so that they age no track; any other pipeline treats every frame on its own, as before."""
+    last batch are padding, so that they age no track; any other pipeline treats every frame on its own, as before.
+    annotate=True: every step is followed by `pipe.draw` on the device (boxes, names, scores; `style`: _lib.DrawStyle), the frames are
+    downloaded once per batch, and the runner yields `(faces, annotated_frame)` pairs -- the reference's output video (main.py:174-184)."""
 
-    def __init__(self, pipe: FacePipeline, gallery: Gallery, frame_hw, similarity_thresh: float = 0.4):
+    def __init__(self, pipe: FacePipeline, gallery: Gallery, frame_hw, similarity_thresh: float = 0.4, annotate: bool = False, style=None):
         self.pipe, self.gallery, self.thr = pipe, gallery, float(similarity_thresh)
+        self.annotate, self.style = bool(annotate), style
         self.H, self.W = int(frame_hw[0]), int(frame_hw[1])
         ctx = pipe.ctx
         shape = (pipe.B, self.H, self.W, 3)
@@ -82,14 +85,21 @@ class StreamRunner:
                 self.pipe.run_step(self.dev[cur], self.H, self.W, self.gallery, self.thr, stream=self.stream[cur].copy())
             else:
                 self.pipe.run_step(self.dev[cur], self.H, self.W, self.gallery, self.thr)
+            if self.annotate:
+                self.pipe.draw(self.dev[cur], self.H, self.W, self.gallery, self.style)   # the step's last reader of the clean frames has run
             check(ctx.lib.fid_upload_release(ctx.handle, cur))     # dev[cur] is free again once this step has run
             nxt = cur ^ 1
             n_nxt = fill(nxt)                                       # host fills the other pinned buffer meanwhile
             if n_nxt:
                 self._upload(nxt)                                   # dev[nxt]'s last reader was step i-1: starts NOW, beside step i
             res = self.pipe.results(self.gallery)                   # synchronises on batch `cur`
-            for r in res[:n_cur]:
-                yield r
+            if self.annotate:
+                drawn = self.dev[cur].download()                    # (dev[cur]'s next upload is enqueued only after this batch has been yielded)
+                for r, frame in zip(res[:n_cur], drawn):
+                    yield r, frame
+            else:
+                for r in res[:n_cur]:
+                    yield r
             cur, n_cur = nxt, n_nxt
 
     def close(self):
