@@ -22,8 +22,9 @@ struct HeadViews {
     long long batch_stride[9];
 };
 
+// (-0.0 takes +0.0's key: numpy's sort compares the two equal and leaves them in index order)
 __device__ __forceinline__ unsigned sortable(float f) {
-    unsigned u = __float_as_uint(f);
+    unsigned u = __float_as_uint(f == 0.f ? 0.f : f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
@@ -295,9 +296,15 @@ __device__ __forceinline__ void nms_select_frame(unsigned char *smem, int b, con
     for (int k = threadIdx.x; k < nkeep; k += blockDim.x) {
         int p = k;
         if (select) {  // np.argsort(values)[::-1][:max_num], stable: larger value first, ties -> larger index first
+            // numpy sorts NaN behind every number, so reversed it comes FIRST (inf - inf of a box with an infinite side), NaNs tie with each other
             const float v = value[k];
+            const bool vnan = v != v;
             int rank = 0;
-            for (int j = 0; j < nkeep; j++) rank += (value[j] > v) || (value[j] == v && j > k);
+            for (int j = 0; j < nkeep; j++) {
+                const float u = value[j];
+                const bool unan = u != u;
+                rank += vnan ? (unan && j > k) : (unan || u > v || (u == v && j > k));
+            }
             p = rank < max_num ? rank : -1;
         }
         if (p < 0 || p >= out_cap) continue;
@@ -353,6 +360,11 @@ static size_t nms_lds_bytes(int cand_cap, int *n_box) {
     if (n_box) *n_box = with_masks ? nb : -nb;                                 // (negative: no mask area behind the boxes)
     return base + (size_t)nb * 16 + (with_masks ? masks : 0);
 }
+// FID_KLOG=1: the two values that pick nms_select's path, as handed to the launch (tests/nms_cases.py mirrors them; n_box as nms_lds_bytes returns it)
+static void klog_nms(int cand_cap, int n_box) {
+    static const bool klog = getenv("FID_KLOG") != nullptr;
+    if (klog) fprintf(stderr, "[klog] nms cand_cap %d n_box %d masks %d\n", cand_cap, n_box < 0 ? -n_box : n_box, n_box > 0 ? 1 : 0);
+}
 // shared by fid_scrfd_postprocess and the fused pipeline
 // tab != NULL: a mixed-size batch -- det_scale and the image size of frame b come from tab[b], img_h / img_w are unused
 // tiles != NULL: tiled detection -- the heads hold T tiles, whose candidates join the lists of the B frames they were cut from (decode_compact_tiled)
@@ -394,6 +406,7 @@ int scrfd_postprocess_launch(fid_ctx *ctx, const HeadViews &hv, int B, int in_h,
     hipLaunchKernelGGL(rank_scatter, g2, dim3(256), 0, ctx->stream, cand_count, keys, data, sorted, cc);
     int n_box = 0;
     const size_t lds = nms_lds_bytes(cc, &n_box);
+    klog_nms(cc, n_box);
     if (tab)
         hipLaunchKernelGGL(nms_select_ragged, dim3(B), dim3(512), lds, ctx->stream, cand_count, sorted, cc, iou, max_num, metric, tab,
                            det_dev, kps_dev, counts_dev, cap, ctx->status_dev, n_box < 0 ? -n_box : n_box, n_box > 0);
@@ -599,6 +612,7 @@ int fid_nms(fid_ctx *ctx, const float *dets_dev, int K, float iou_thres, int32_t
     hipLaunchKernelGGL(rank_scatter, dim3(fid::cdiv(cc, 256), 1), dim3(256), 0, ctx->stream, cand_count, keys, data, sorted, cc);
     int n_box = 0;
     const size_t lds = fid::nms_lds_bytes(cc, &n_box);
+    fid::klog_nms(cc, n_box);
     FID_TRY(fid::ensure_dyn_lds(ctx, (const void *)nms_select, (int)std::max<size_t>(lds, fid::nms_lds_bytes(ctx->cand_cap, nullptr))));
     hipLaunchKernelGGL(nms_select, dim3(1), dim3(512), lds, ctx->stream, cand_count, sorted, cc, iou_thres, 0, 0, 1, 1,
                        (float *)nullptr, (float *)nullptr, count_dev, K, keep_dev, ctx->status_dev + 4, n_box < 0 ? -n_box : n_box, n_box > 0);
