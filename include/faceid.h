@@ -409,6 +409,65 @@ int fid_face_gates(fid_ctx *ctx, const float *det_dev, const float *kps_dev, con
                    int faces_per_frame, const double *pose_dev, const fid_gate_config *cfg, float *quality_dev,
                    int32_t *side_dev, int32_t *best_dev);
 
+/* ---- measured face quality: sharpness, exposure and pose of every aligned crop, on the device.  (No reference analogue: assess_face_quality,
+ * smart_face_recognition.py:1145-1216, sets blur = min(1, det_score * 1.2) and lighting = min(1, det_score * 1.1) without reading a pixel, and
+ * is_side_face reads face.yaw / face.pitch, which SCRFD never provides.)  Opt-in: nothing calls these unless asked to.
+ *
+ * fid_face_measure: one launch over a table of crops.  crops_dev uint8 [n_rows,112,112,3] BGR as fid_align_crops* writes them.  src_dev (may be
+ * NULL) is the row table of fid_face_pack / fid_track_step: a row with src[i] < 0 is no face, its crop bytes are ignored and all 16 of its
+ * output words are 0; row i reads the landmarks kps[src[i]*10 ..]; with src == NULL every row is a face and reads kps[i*10 ..].  kps_dev and
+ * M_dev (row i = the 6 doubles fid_align_crops* writes) may both be NULL: then only the pixel part is computed.
+ * Pixel part, all integer, so independent of the order of summation:
+ *   Y = (29*B + 150*G + 77*R + 128) >> 8;  window = the 80 x 80 pixels with 16 <= x, y < 96 (N = 6400: it holds all five template landmarks and
+ *   leaves out most background and most of the warp's zero border);  L = 4*Y(x,y) - Y(x-1,y) - Y(x+1,y) - Y(x,y-1) - Y(x,y+1) on every window
+ *   pixel, neighbours at coordinate 15 and 96 read from the crop.
+ *   stats int64 [n_rows,8] = N, sum Y, sum Y^2, sum L, sum L^2, n_dark (Y <= 16), n_bright (Y >= 239), flags (bit 0: pixel part valid, bit 1:
+ *   pose part valid).
+ * measure float [n_rows,8], each word computed in fp64 from the integers -- the integer expression in int64, converted once to double, one
+ * correctly rounded divide (and square root) -- and rounded once to fp32:
+ *   0 sharpness = (N*sum L^2 - (sum L)^2) / (N*N)          the variance of the Laplacian
+ *   1 mean      = sum Y / N
+ *   2 contrast  = sqrt((N*sum Y^2 - (sum Y)^2) / (N*N))
+ *   3 clipped   = (n_dark + n_bright) / N
+ * Pose part, fp64 with + - * / and square root only, every operation rounded separately, no FMA.  k_i = landmark i widened to double, t_i = the
+ * float32 ArcFace template widened to double (as the warp sees it);  p_i.x = (M0*k_i.x + M1*k_i.y) + M2,  p_i.y = (M3*k_i.x + M4*k_i.y) + M5.
+ * For a point set q:  ex = (q0.x+q1.x)/2, ey = (q0.y+q1.y)/2, mx = (q3.x+q4.x)/2, my = (q3.y+q4.y)/2, w = q1.x - q0.x, h = my - ey,
+ * Ry(q) = (q2.x - (ex+mx)/2) / w,  Rp(q) = (q2.y - ey) / h.
+ *   4 yaw      = Ry(p) - Ry(t)     the nose's offset from the face's vertical axis in eye widths; positive: towards +x in the crop
+ *   5 pitch    = Rp(p) - Rp(t)
+ *   6 residual = sqrt(sum_i((p_i.x-t_i.x)^2 + (p_i.y-t_i.y)^2) / 5)    i = 0 .. 4 left to right: RMS misfit to the template, in crop pixels
+ *   7 0
+ * The pose part is valid iff landmarks and M are given, all six entries of M are finite, w(p) > 0 and h(p) > 0, and the three fp32 words are
+ * finite; otherwise the three words are 0 and flag bit 1 is clear.  Ratios, not angles: no transcendental function, so device, host and a
+ * numpy restatement agree to the bit.
+ * n_rows == 0 returns FID_OK and enqueues nothing.  FID_E_INVALID: n_rows < 0, a NULL ctx, crops or output pointer, exactly one of kps / M.
+ * Asynchronous on the context's stream; it never synchronises with the host.  n_rows is not limited to 65535.
+ * fid_face_measure_host: the same definition in plain loops on HOST arrays, no device involved. */
+int fid_face_measure(fid_ctx *ctx, const uint8_t *crops_dev, int n_rows, const float *kps_dev, const int32_t *src_dev, const double *M_dev,
+                     int64_t *stats_dev, float *measure_dev);
+int fid_face_measure_host(const uint8_t *crops, int n_rows, const float *kps, const int32_t *src, const double *M, int64_t *stats,
+                          float *measure);
+/* fid_face_gates with measured scores.  Same outputs, layouts, best-face rule and verdict order as fid_face_gates; no pose input.  Face f of
+ * frame b reads row offsets[b] + f of stats / measure (offsets_dev: fid_face_pack's format, the row form of fid_draw_faces), or row
+ * b * faces_per_frame + f when offsets_dev is NULL.  A face whose row is < 0 or >= n_rows gets exactly what fid_face_gates computes for it
+ * (n_rows = 0: every face; stats and measure may then be NULL), and so does each part whose flag bit is clear: bit 0 for blur and lighting,
+ * bit 1 for pose and the landmark side test.  fp32, one rounded operation each:
+ *   blur     = min(1, sharpness / sharpness_normalization)
+ *   lighting = min(1, contrast / contrast_normalization) * (1 - clipped)
+ *   pose     = max(0, 1 - residual / residual_normalization)
+ * size, the detection term and the weighted sum are fid_face_gates'.  Side flag: the bounding-box analysis (score >= decision_threshold), OR
+ * |yaw| > yaw_ratio_threshold, OR |pitch| > pitch_ratio_threshold (both strict, fp32).
+ * The defaults the Python binding suggests (100, 40, 8 pixels, 0.25, 0.25) are UNCALIBRATED: nobody has measured them on real faces; they are
+ * starting points for a user's own calibration. */
+typedef struct fid_measure_config {
+    float sharpness_normalization, contrast_normalization, residual_normalization;
+    float yaw_ratio_threshold, pitch_ratio_threshold;
+} fid_measure_config;
+int fid_face_gates_measured(fid_ctx *ctx, const float *det_dev, const float *kps_dev, const int32_t *counts_dev, int B, int cap,
+                            int faces_per_frame, const int64_t *stats_dev, const float *measure_dev, const int32_t *offsets_dev,
+                            int n_rows, const fid_gate_config *cfg, const fid_measure_config *mcfg,
+                            float *quality_dev, int32_t *side_dev, int32_t *best_dev);
+
 /* ---- embeddings -> unit fp16 rows: the norm half of reference utils/helpers.py:120-123 ------
  * A row whose fp32 sum of squares is not in (0, inf) -- all zero, a NaN or inf element, squares that overflow or underflow -- becomes an all +0.0 row. */
 int fid_l2_normalize_f16(fid_ctx *ctx, const float *emb_dev, int n, int dim, void *out_f16_dev);

@@ -102,6 +102,23 @@ class DrawStyle(C.Structure):
         self.unknown_bgr[:3] = [int(v) for v in unknown_bgr]
 
 
+MEASURE_KEYS = ("sharpness", "mean", "contrast", "clipped", "yaw", "pitch", "residual")       # words 0 .. 6 of a fid_face_measure row
+MEASURE_PIXELS_VALID, MEASURE_POSE_VALID = 1, 2                                                # stats word 7
+
+
+class MeasureConfig(C.Structure):
+    """fid_measure_config (include/faceid.h): what fid_face_gates_measured divides the measured sharpness (variance of the Laplacian), contrast
+    (standard deviation of the luma) and landmark residual (crop pixels) by, and the |yaw| / |pitch| ratios above which a face is a side face.
+    The defaults are UNCALIBRATED: nobody has measured them on real faces.  They are starting points for a user's own calibration."""
+    _fields_ = [(n, C.c_float) for n in ("sharpness_normalization", "contrast_normalization", "residual_normalization",
+                                         "yaw_ratio_threshold", "pitch_ratio_threshold")]
+
+    def __init__(self, sharpness_normalization=100.0, contrast_normalization=40.0, residual_normalization=8.0, yaw_ratio_threshold=0.25,
+                 pitch_ratio_threshold=0.25):
+        super().__init__(float(sharpness_normalization), float(contrast_normalization), float(residual_normalization),
+                         float(yaw_ratio_threshold), float(pitch_ratio_threshold))
+
+
 def label_arrays(names, colors=None):
     """names (str or bytes per gallery row), colors (BGR triple per row, or None) as fid_labels_create / fid_draw_faces_host take them:
     (name bytes, int32 [G+1] offsets, uint8 [G,3] or None).  A str is encoded as UTF-8; the table keeps FID_LABEL_MAX bytes of it."""
@@ -194,6 +211,10 @@ SIGNATURES = {
                                      C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "fid_face_gates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
+    "fid_face_measure": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fid_face_measure_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fid_face_gates_measured": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fid_gallery_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_void_pp]),
     "fid_gallery_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "fid_gallery_info": (C.c_int, [C.c_void_p, c_int_p, c_int_p, c_int_p]),

@@ -11,23 +11,55 @@ from typing import List, Optional
 
 import numpy as np
 
-from ._lib import GateConfig, check
+from ._lib import MEASURE_KEYS, GateConfig, MeasureConfig, check
 from .models import ArcFace, SCRFD
 
 VERDICTS = ("accepted", "no face", "confidence too low", "side face", "quality too low")      # FID_GATE_* (include/faceid.h)
 QUALITY_KEYS = ("overall", "blur", "pose", "lighting", "size")
 
 
-def face_gates(ctx, det_dev, kps_dev, counts_dev, batch: int, cap: int, faces_per_frame: int, config: Optional[GateConfig] = None, pose=None):
+def face_measure(ctx, crops, n_rows: int, kps=None, src=None, M=None):
+    """fid_face_measure on device buffers: sharpness, exposure and pose of the first `n_rows` aligned crops (uint8 [*,112,112,3] as the
+    fid_align_crops* calls write them).  src: the row table (int32, a row < 0 is no face); kps / M: the landmarks the rows pick from and
+    the rows' similarity matrices, both or neither.  Asynchronous.  -> (stats int64 [n_rows,8], measure float32 [n_rows,8]) on the device"""
+    from ._lib import _ptr
+    stats, measure = ctx.empty((n_rows, 8), np.int64), ctx.empty((n_rows, 8), np.float32)
+    check(ctx.lib.fid_face_measure(ctx.handle, _ptr(crops), n_rows, _ptr(kps) if kps is not None else None,
+                                   _ptr(src) if src is not None else None, _ptr(M) if M is not None else None, C.c_void_p(stats.ptr),
+                                   C.c_void_p(measure.ptr)))
+    return stats, measure
+
+
+def measured_dicts(stats: np.ndarray, measure: np.ndarray):
+    """host copies of fid_face_measure's outputs -> per row a dict keyed by MEASURE_KEYS, or None for a row that is no face"""
+    return [dict(zip(MEASURE_KEYS, (float(v) for v in measure[i, :7]))) if stats[i, 7] & 1 else None for i in range(len(stats))]
+
+
+def face_gates(ctx, det_dev, kps_dev, counts_dev, batch: int, cap: int, faces_per_frame: int, config: Optional[GateConfig] = None, pose=None,
+               measures=None, offsets=None, measure_config: Optional[MeasureConfig] = None):
     """The reference's quality / side-face gates and best-face selection (smart_face_recognition.py:1145-1216, 1218-1297, 1299-1399,
     1473-1519) for every face of a batch, on the post-process's device arrays (`PostProcessor.det / .kps / .counts`, cap = their
     second dimension).  pose: optional [batch, faces_per_frame, 2] yaw / pitch in radians (0 = not available), handed over as float64.
+    measures: optional (stats, measure) device buffers of face_measure -- then fid_face_gates_measured decides, with blur, lighting, pose and
+    the side test measured for every face whose row carries them: face f of frame b is row offsets[b] + f (offsets: the device table of
+    fid_face_pack) or, without offsets, row b * faces_per_frame + f; measure_config: the MeasureConfig (its defaults are uncalibrated).
     -> quality [batch, F, 5] (QUALITY_KEYS), side score [batch, F], side flag [batch, F] (bool), best [batch, 2] = (face index or -1, verdict)"""
     cfg = config or GateConfig()
     F = faces_per_frame
     quality = ctx.empty((batch, F, 5), np.float32)
     side = ctx.empty((batch, F), np.int32)
     best = ctx.empty((batch, 2), np.int32)
+    if measures is not None:
+        if pose is not None:
+            raise ValueError("face_gates: measured gates take no pose angles")
+        stats, measure = measures
+        mcfg = measure_config or MeasureConfig()
+        check(ctx.lib.fid_face_gates_measured(ctx.handle, C.c_void_p(det_dev.ptr), C.c_void_p(kps_dev.ptr), C.c_void_p(counts_dev.ptr), batch, cap, F,
+                                              C.c_void_p(stats.ptr), C.c_void_p(measure.ptr), C.c_void_p(offsets.ptr) if offsets is not None else None,
+                                              min(stats.shape[0], measure.shape[0]), C.byref(cfg), C.byref(mcfg), C.c_void_p(quality.ptr),
+                                              C.c_void_p(side.ptr), C.c_void_p(best.ptr)))
+        sd = side.download()
+        return quality.download(), sd & 0xFFFF, (sd >> 16).astype(bool), best.download()
     pose_dev = ctx.to_device(np.ascontiguousarray(pose, dtype=np.float64).reshape(batch, F, 2)) if pose is not None else None   # (float64 across the boundary: python floats in the reference)
     check(ctx.lib.fid_face_gates(ctx.handle, C.c_void_p(det_dev.ptr), C.c_void_p(kps_dev.ptr), C.c_void_p(counts_dev.ptr), batch, cap, F,
                                  C.c_void_p(pose_dev.ptr) if pose_dev is not None else None, C.byref(cfg), C.c_void_p(quality.ptr),
@@ -55,12 +87,19 @@ class Face(dict):
 
 class FaceAnalysis:
     def __init__(self, det_model: str = "synthetic:scrfd_10g", rec_model: str = "synthetic:arcface_r50", *, device: int = 0,
-                 det_size=(640, 640), det_thresh: float = 0.5, max_faces: int = 64, gate_config: Optional[GateConfig] = None):
+                 det_size=(640, 640), det_thresh: float = 0.5, max_faces: int = 64, gate_config: Optional[GateConfig] = None,
+                 measured_quality: bool = False, measure_config: Optional[MeasureConfig] = None):
+        """measured_quality: get / get_batch measure every aligned crop (fid_face_measure: sharpness, exposure, pose) right behind the warp,
+        gate with the measured scores (fid_face_gates_measured, `measure_config`: a MeasureConfig, whose defaults are uncalibrated) and give
+        each Face a `measured` dict keyed by MEASURE_KEYS; best_face / process_visits then reject on measured quality through the unchanged
+        verdict path.  Off (the default): no `measured` key, nothing new is launched."""
         self.det = SCRFD(det_model, input_size=det_size, conf_thres=det_thresh, device=device)
         self.rec = ArcFace(rec_model, device=device, ctx=self.det.ctx, max_batch=max_faces)
         self.ctx = self.det.ctx
         self.max_faces = int(max_faces)
         self.gate_config = gate_config or GateConfig()       # the reference's config.json thresholds (GateConfig.from_reference_json)
+        self.measured_quality = bool(measured_quality)
+        self.measure_config = measure_config or MeasureConfig()
         self.last_verdict = None                              # of the last best_face(): one of VERDICTS
         self.last_batch_best = []                             # of the last get_batch(): per image (best face index, FID_GATE_* verdict)
 
@@ -90,8 +129,10 @@ class FaceAnalysis:
         kp = ctx.to_device(np.ascontiguousarray(kpss[:n], dtype=np.float32).reshape(1, n, 10))
         cn = ctx.to_device(np.array([n], np.int32))
         crops = ctx.empty((n, 112, 112, 3), np.uint8)
+        Mm = ctx.empty((n, 6), np.float64) if self.measured_quality else None
         check(ctx.lib.fid_align_crops(ctx.handle, C.c_void_p(fr.ptr), 1, H, W, C.c_void_p(kp.ptr), C.c_void_p(cn.ptr), n, n,
-                                      C.c_void_p(crops.ptr), None))
+                                      C.c_void_p(crops.ptr), C.c_void_p(Mm.ptr) if Mm is not None else None))
+        measures = face_measure(ctx, crops, n, kps=kp, M=Mm) if self.measured_quality else None
         net = self.rec.session.compiled()
         net.run_device(crops, n)
         emb_ptr, _, _ = net.tensor(net.low.outputs[0])
@@ -101,11 +142,16 @@ class FaceAnalysis:
         normed = q.download().astype(np.float32)
         # quality scores, side-face flag and the best-face verdict of the reference's product layer, all faces in one launch
         dd = ctx.to_device(np.ascontiguousarray(det[:n], dtype=np.float32).reshape(1, n, 5))
-        quality, side_score, side_flag, best = face_gates(ctx, dd, kp, cn, 1, n, n, self.gate_config)
+        quality, side_score, side_flag, best = face_gates(ctx, dd, kp, cn, 1, n, n, self.gate_config, measures=measures,
+                                                          measure_config=self.measure_config)
         self._best = (int(best[0, 0]), int(best[0, 1]))
-        return [Face(bbox=det[i, :4].copy(), det_score=float(det[i, 4]), kps=kpss[i].copy(), embedding=emb[i].copy(),
-                     normed_embedding=normed[i].copy(), quality={k: float(quality[0, i, j]) for j, k in enumerate(QUALITY_KEYS)},
-                     is_side_face=bool(side_flag[0, i]), side_face_score=int(side_score[0, i])) for i in range(n)]
+        faces = [Face(bbox=det[i, :4].copy(), det_score=float(det[i, 4]), kps=kpss[i].copy(), embedding=emb[i].copy(),
+                      normed_embedding=normed[i].copy(), quality={k: float(quality[0, i, j]) for j, k in enumerate(QUALITY_KEYS)},
+                      is_side_face=bool(side_flag[0, i]), side_face_score=int(side_score[0, i])) for i in range(n)]
+        if measures is not None:
+            for f, m in zip(faces, measured_dicts(measures[0].download(), measures[1].download())):
+                f["measured"] = m
+        return faces
 
     def get_batch(self, images, max_num: int = 0) -> List[List[Face]]:
         """get() for a batch of images ([B,H,W,3], or a list whose images may differ in size: then every chunk is one mixed-size batch,
@@ -147,29 +193,43 @@ class FaceAnalysis:
             normed = np.empty((total, 512), np.float32)
             rows = min(total, self.max_faces)
             crops, q = ctx.empty((rows, 112, 112, 3), np.uint8), ctx.empty((rows, 512), np.float16)
+            measures = None
+            if self.measured_quality:                         # M of one run; stats / measure of the whole chunk, filled run by run
+                Mm = ctx.empty((rows, 6), np.float64)
+                measures = (ctx.empty((total, 8), np.int64), ctx.empty((total, 8), np.float32))
             for r0 in range(0, total, self.max_faces):
                 n = min(self.max_faces, total - r0)
                 src_n = C.c_void_p(src.ptr + 4 * r0)
+                M_n = C.c_void_p(Mm.ptr) if measures is not None else None
                 if mixed:
                     check(lib.fid_align_crops_packed_ragged(ctx.handle, *batch.args(), B, C.c_void_p(post.kps.ptr), post.cap, src_n, n,
-                                                            C.c_void_p(crops.ptr), None))
+                                                            C.c_void_p(crops.ptr), M_n))
                 else:
                     check(lib.fid_align_crops_packed(ctx.handle, C.c_void_p(fr.ptr), B, H, W, C.c_void_p(post.kps.ptr), post.cap, src_n, n,
-                                                     C.c_void_p(crops.ptr), None))
+                                                     C.c_void_p(crops.ptr), M_n))
+                if measures is not None:                      # the crop buffer is reused per run: measure it before the next warp
+                    check(lib.fid_face_measure(ctx.handle, C.c_void_p(crops.ptr), n, C.c_void_p(post.kps.ptr), src_n, M_n,
+                                               C.c_void_p(measures[0].ptr + 64 * r0), C.c_void_p(measures[1].ptr + 32 * r0)))
                 net.run_device(crops, n)
                 emb_ptr, _, _ = net.tensor(net.low.outputs[0])
                 check(lib.fid_l2_normalize_f16_packed(ctx.handle, C.c_void_p(emb_ptr), n, 512, src_n, C.c_void_p(q.ptr)))
                 emb[r0:r0 + n] = net.read(net.low.outputs[0], n).reshape(n, 512)
                 normed[r0:r0 + n] = q.download()[:n].astype(np.float32)
             F = max(len(d) for d, _ in dets)
-            quality, side_score, side_flag, best = face_gates(ctx, post.det, post.kps, post.counts, B, post.cap, F, self.gate_config)
+            quality, side_score, side_flag, best = face_gates(ctx, post.det, post.kps, post.counts, B, post.cap, F, self.gate_config,
+                                                              measures=measures, offsets=offsets if measures is not None else None,
+                                                              measure_config=self.measure_config)
             bests += [(int(i), int(v)) for i, v in best]
             off = offsets.download()
+            md = measured_dicts(measures[0].download(), measures[1].download()) if measures is not None else None
             for b, (det, kpss) in enumerate(dets):
                 r = int(off[b])
                 out.append([Face(bbox=det[i, :4].copy(), det_score=float(det[i, 4]), kps=kpss[i].copy(), embedding=emb[r + i].copy(),
                                  normed_embedding=normed[r + i].copy(), quality={k: float(quality[b, i, j]) for j, k in enumerate(QUALITY_KEYS)},
                                  is_side_face=bool(side_flag[b, i]), side_face_score=int(side_score[b, i])) for i in range(len(det))])
+                if md is not None:
+                    for i, f in enumerate(out[-1]):
+                        f["measured"] = md[r + i]
         self.last_batch_best = bests
         return out
 

@@ -372,12 +372,15 @@ class PackedFacePipeline(FacePipeline):
                           smallest entry of `buckets` >= min(total, row_cap) rows; no face at all -> recogniser and match are skipped.
     buckets   ascending row counts ending in row_cap (default: the multiples of 64).  The executor tunes and plans per batch size, so
               the set of sizes it ever sees must be small and fixed; warm() runs each once.
+    measure   True: embed() asks the warp for the similarity matrices and measures the rows right behind it on the same stream
+              (fid_face_measure: sharpness, exposure, pose); `stats` / `measures` hold [row_cap, 8] on the device, results_measured() reads
+              them.  results() is the same either way.
     More survivors than det_cap in one frame is FID_E_CAPACITY from results(), as in FacePipeline.  Rows of q / idx / score at or past
     the rows of the last step (`n_run`) are stale.  Single device: the distributed step and step grouping know nothing of row tables."""
 
     def __init__(self, ctx: Context, det: CompiledNet, rec: CompiledNet, *, batch: int, row_cap: int, max_num: int = 0,
                  rows: str = "capacity", buckets: Optional[Sequence[int]] = None, conf_thres: float = 0.5, iou_thres: float = 0.4,
-                 metric: int = 0, det_cap: int = 256, q_buffer=None, tiling=None):
+                 metric: int = 0, det_cap: int = 256, q_buffer=None, tiling=None, measure: bool = False):
         assert det.max_batch >= batch and rec.max_batch >= row_cap and 0 < row_cap <= 65535 and max_num >= 0
         if rows not in ("capacity", "count"):
             raise ValueError(f"rows must be 'capacity' or 'count', not {rows!r}")
@@ -399,6 +402,12 @@ class PackedFacePipeline(FacePipeline):
         self.q = q_buffer if q_buffer is not None else ctx.empty((self.row_cap, self.emb_dim), np.float16)
         self.idx = ctx.empty((self.row_cap,), np.int32)
         self.score = ctx.empty((self.row_cap,), np.float32)
+        self.measure = bool(measure)
+        self.M = self.stats = self.measures = None
+        if self.measure:
+            self.M = ctx.empty((self.row_cap, 6), np.float64)
+            self.stats = ctx.empty((self.row_cap, 8), np.int64)
+            self.measures = ctx.empty((self.row_cap, 8), np.float32)
         self._det_in = None
         self._hv: Optional[HeadViews] = None
         self._set_tiling(tiling)                              # (FacePipeline: detect() tiles every frame when set)
@@ -427,7 +436,10 @@ class PackedFacePipeline(FacePipeline):
             self.n_run = self.row_cap
         n = self.n_run
         check(lib.fid_align_crops_packed(h, _lib._ptr(frames_dev), self.B, H, W, C.c_void_p(self.post.kps.ptr), self.post.cap,
-                                         C.c_void_p(self.src.ptr), n, C.c_void_p(self.crops.ptr), None))
+                                         C.c_void_p(self.src.ptr), n, C.c_void_p(self.crops.ptr), C.c_void_p(self.M.ptr) if self.measure else None))
+        if self.measure:
+            check(lib.fid_face_measure(h, C.c_void_p(self.crops.ptr), n, C.c_void_p(self.post.kps.ptr), C.c_void_p(self.src.ptr),
+                                       C.c_void_p(self.M.ptr), C.c_void_p(self.stats.ptr), C.c_void_p(self.measures.ptr)))
         self.rec.run_device(self.crops, n)
         self.rec_steps += 1
         emb_ptr, _, _ = self.rec.tensor(self.rec.low.outputs[0])
@@ -482,6 +494,26 @@ class PackedFacePipeline(FacePipeline):
                               gallery.names[j] if j >= 0 else "Unknown", float(score[i])))
             out.append(faces)
         return out
+
+    def _measured_rows(self):
+        """per row of the last step's table a MEASURE_KEYS dict, None for a row that holds no face or was not run"""
+        if not self.measure:
+            raise RuntimeError("results_measured needs a pipeline built with measure=True")
+        n = min(self.n_run, self.row_cap)
+        rows = [None] * self.row_cap
+        if n > 0:
+            stats, meas = self.stats.download()[:n], self.measures.download()[:n]
+            for i in range(n):
+                if stats[i, 7] & 1:
+                    rows[i] = dict(zip(_lib.MEASURE_KEYS, (float(v) for v in meas[i, :7])))
+        return rows
+
+    def results_measured(self, gallery: Gallery):
+        """(results(gallery), measured): measured[b][f] is the MEASURE_KEYS dict of face f of frame b as results() lists it"""
+        res = self.results(gallery)
+        rows = self._measured_rows()
+        offsets, _ = packed_layout(self.post.counts.download()[:self.B], self.post.cap, self.max_num, self.row_cap)
+        return res, [[rows[int(offsets[b]) + f] for f in range(len(res[b]))] for b in range(self.B)]
 
     @property
     def overflow(self) -> int:
@@ -627,6 +659,16 @@ class TrackedFacePipeline(PackedFacePipeline):
         """the list FacePipeline.results gives -- (bbox[4], det_score, kps[5,2], name, similarity) -- for every detection, name and
         similarity taken from its track"""
         return [[face[:5] for face in frame] for frame in self.results_tracked(gallery)]
+
+    def results_measured(self, gallery: Optional[Gallery] = None):
+        """(results(gallery), measured): measured[b][f] is the MEASURE_KEYS dict of detection f of frame b if it was embedded in this step (the
+        tracker's rows are the faces embedded now), else None"""
+        res = self.results(gallery)
+        rows = self._measured_rows()
+        src = self.src.download()
+        n, cap = min(self.n_run, self.row_cap), self.post.cap
+        row_of = {int(src[i]): i for i in range(n) if src[i] >= 0}
+        return res, [[rows[row_of[b * cap + f]] if b * cap + f in row_of else None for f in range(len(res[b]))] for b in range(self.B)]
 
     def embeddings(self) -> Tuple[np.ndarray, np.ndarray]:
         """Raw fp32 embeddings of the rows the last step ran, [rows, 512] in table order, and the table's offsets [B+1] (src says whose)."""

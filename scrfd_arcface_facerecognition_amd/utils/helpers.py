@@ -118,6 +118,29 @@ def match_gallery(embeddings, gallery, thresh, *, ctx=None, return_matrix=False)
     return out
 
 
+# ---- measured face quality (no reference analogue: its blur and lighting scores read no pixel) ----
+def measure_crops(crops, kps=None, M=None):
+    """fid_face_measure_host on numpy arrays, no device: crops uint8 [n,112,112,3] (or one [112,112,3]) BGR as norm_crop_image returns them;
+    optionally the landmarks [n,5,2] and the matrices estimate_norm returns [n,2,3], both or neither.
+    -> per crop a dict keyed by MEASURE_KEYS (python floats holding the float32 words) plus "pose_valid"."""
+    from .._lib import MEASURE_KEYS, MEASURE_POSE_VALID, load
+    crops = np.ascontiguousarray(crops, dtype=np.uint8)
+    if crops.ndim == 3:
+        crops = crops[None]
+    if crops.ndim != 4 or crops.shape[1:] != (112, 112, 3):
+        raise ValueError(f"measure_crops needs uint8 [n,112,112,3] crops, not {crops.shape}")
+    if (kps is None) != (M is None):
+        raise ValueError("measure_crops: landmarks and M come together or not at all")
+    n = len(crops)
+    k = None if kps is None else np.ascontiguousarray(kps, dtype=np.float32).reshape(n, 10)
+    m = None if M is None else np.ascontiguousarray(M, dtype=np.float64).reshape(n, 6)
+    stats, meas = np.zeros((n, 8), np.int64), np.zeros((n, 8), np.float32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    check(load().fid_face_measure_host(p(crops), n, p(k), None, p(m), p(stats), p(meas)))
+    return [dict({key: float(meas[i, j]) for j, key in enumerate(MEASURE_KEYS)}, pose_valid=bool(stats[i, 7] & MEASURE_POSE_VALID))
+            for i in range(n)]
+
+
 # ---- drawing (reference utils/helpers.py:126-179): with OpenCV on the host, cv2's primitives; without it, the library's host rasteriser
 # (fid_draw_faces_host: the raster rules of include/faceid.h -- the same pixels fid_draw_faces writes on the device) ----
 def _cv2():
