@@ -468,6 +468,75 @@ int fid_face_gates_measured(fid_ctx *ctx, const float *det_dev, const float *kps
                             int n_rows, const fid_gate_config *cfg, const fid_measure_config *mcfg,
                             float *quality_dev, int32_t *side_dev, int32_t *best_dev);
 
+/* ---- best shots: of the faces a track embeds, keep the best one on the device; hand an ended track out as one finished visit.  (No reference
+ * analogue: the reference embeds and matches every face of every frame and forgets; its visits come from files.)  Opt-in: nothing calls
+ * these unless asked to.
+ *
+ * fid_shot_score: one fp32 score per row of fid_face_measure's output, one thread per row.  fp32, every operation rounded on its own, no FMA,
+ * correctly rounded divides -- fid_face_gates_measured's three terms from the same fid_measure_config fields (as UNCALIBRATED as they are there):
+ *   b = min(1, sharpness / sharpness_normalization)
+ *   l = min(1, contrast / contrast_normalization) * (1 - clipped)
+ *   p = max(0, 1 - residual / residual_normalization)
+ *   score = (b * l) * p        (min / max as `x < 1 ? x : 1` / `x > 0 ? x : 0`; a NaN result is written as the quiet NaN 0x7FC00000)
+ * Flags (stats word 7): bit 0 clear (no face, or no valid pixel part): score -1.0f, the row is never a candidate.  Bit 1 clear: p = 0, so the
+ * score is 0: still a candidate, but the weakest.  n_rows == 0: FID_OK, nothing enqueued.  FID_E_INVALID: a NULL pointer, n_rows < 0, a
+ * normalisation that is not finite and > 0.  fid_shot_score_host: the same function on HOST arrays, no device involved.
+ *
+ * A keeper (fid_shots) belongs to a tracker's shape: S streams x T slots, embeddings of `dim` fp16 values.  All state is in device memory:
+ * the live store (S x T entries: meta, q, and the crop if keep_crops), the finished store (finished_cap entries of the same record, plus
+ * count and dropped) and a frame counter per stream.  Meta, int32 x FID_SHOT_META_WORDS:
+ *   0 stream   1 track id (-1: an empty entry, then every other word is 0)   2 ident_idx   3 bits of ident_score   4 bits of the shot's score
+ *   (-1.0f: the track has had no candidate row yet; then words 5 and 7 .. 11 are 0)   5 frame number of the shot   6 rows of this track seen
+ *   so far   7 .. 10 bits of the shot's box   11 bits of its detection score   12 .. 15 0.
+ * The frame number is the stream's count of non-skipped frames over all keep calls since create, 0-based.
+ *
+ * fid_track_keep follows one completed step, i.e. a step after its fid_track_identify, with the step's stream, sizes, track, offsets and src
+ * again, any float score[n_rows] (fid_shot_score's or the caller's own), the step's unit fp16 rows q_dev [n_rows,dim], its crops
+ * [n_rows,112,112,3] (may be NULL without keep_crops), det_dev [B,cap,5] and optionally fid_track_identify's ident_idx / ident_score [B,cap].
+ * Per stream s, over the step's rows i < min(offsets[B], n_rows, row_cap) in table order whose frame b = src[i] / cap has stream[b] == s:
+ *   1. a row whose track word is negative is untracked and is skipped.
+ *   2. otherwise the row has (slot, id).  If the live entry of (s, slot) holds another id -- or the same id while the row carries
+ *      FID_TRACK_STARTED: after fid_tracker_reset a stream's ids begin again at 0 --, that entry FINISHES NOW: it is appended to the
+ *      finished store and the entry becomes empty.  An empty entry begins the track: id, ident (-1, 0), score -1.0f, rows 0.
+ *   3. rows += 1; with identity arrays, words 2 and 3 become ident_idx / ident_score at src[i]: the track's name as of its latest row,
+ *      whichever row is the best shot.
+ *   4. the row is a CANDIDATE iff score[i] >= 0 (false for a NaN).  A candidate replaces the entry's shot iff the entry has no shot yet for
+ *      this id, or score[i] > the stored score (strict: on a tie the earlier row stays).  A replacement copies score, frame number, box,
+ *      detection score, q row and crop.
+ *   5. after the stream's rows, slots 0 .. T-1 ascending: a live entry whose id is not the id the tracker's slot holds now finishes (a freed,
+ *      reset or reused slot).  This runs for every stream, with or without frames in the step.
+ *   6. a track that never had a candidate row finishes without a record.
+ * The finished order is streams ascending, within a stream the order above.  With the finished store full the record is dropped and
+ * dropped += 1; the live entry is cleared all the same.  Skipping the keep for a step is allowed; the tracks that started and ended unseen
+ * leave no record.
+ * fid_shots_flush finishes every live entry of the stream in slot order (-1: all streams in stream order): the end of a video.
+ * fid_shots_finished (synchronises) reads count and dropped and hands out the finished store's device arrays: meta int32 [finished_cap,16],
+ * q fp16 [finished_cap,dim] -- rows 0 .. count-1 are fid_gallery_group's queries where they lie -- crops uint8 [finished_cap,112,112,3] (NULL
+ * without keep_crops); each out-pointer may be NULL.  fid_shots_clear_finished sets count and dropped to 0.  fid_shots_read (synchronises; tests
+ * and debugging): the live meta, int32 [S,T,16].
+ * FID_E_INVALID, nothing enqueued, state untouched: a NULL required pointer; S or T outside the tracker's ranges (and S * 64 * 16 must fit
+ * int32) or different from the tracker's; dim < 1; finished_cap < 1; crops_dev == NULL with keep_crops; exactly one of the identity arrays;
+ * n_rows outside [0, row_cap]; B, cap, row_cap or a stream array that differ from the tracker's last step's; a tracker that has run no step,
+ * or whose step still waits for its identify; a second keep for the same step (the tracker counts its steps; the keeper remembers the last
+ * one it saw); a flush of a stream outside [-1, S).
+ * fid_track_keep and fid_shots_flush are asynchronous on the context's stream and never synchronise with the host (the keeper's event table
+ * grows by allocation alone when n_rows outgrows it, 1024 rows at first). */
+typedef struct fid_shots fid_shots;
+#define FID_SHOT_META_WORDS 16
+int fid_shot_score(fid_ctx *ctx, const int64_t *stats_dev, const float *measure_dev, int n_rows, const fid_measure_config *mcfg,
+                   float *score_dev);
+int fid_shot_score_host(const int64_t *stats, const float *measure, int n_rows, const fid_measure_config *mcfg, float *score);
+int fid_shots_create(fid_ctx *ctx, int S, int T, int dim, int finished_cap, int keep_crops, fid_shots **out);
+int fid_shots_destroy(fid_ctx *ctx, fid_shots *shots);
+int fid_track_keep(fid_ctx *ctx, fid_shots *shots, fid_tracker *trk, const int32_t *stream, int B, int cap, const int32_t *track_dev,
+                   const int32_t *offsets_dev, const int32_t *src_dev, int row_cap, int n_rows, const float *score_dev, const uint16_t *q_dev,
+                   const uint8_t *crops_dev, const float *det_dev, const int32_t *ident_idx_dev, const float *ident_score_dev);
+int fid_shots_flush(fid_ctx *ctx, fid_shots *shots, int stream);
+int fid_shots_finished(fid_ctx *ctx, fid_shots *shots, int32_t *count, int32_t *dropped, const int32_t **meta_dev, const uint16_t **q_dev,
+                       const uint8_t **crops_dev);
+int fid_shots_clear_finished(fid_ctx *ctx, fid_shots *shots);
+int fid_shots_read(fid_ctx *ctx, fid_shots *shots, int32_t *live_meta_host);
+
 /* ---- embeddings -> unit fp16 rows: the norm half of reference utils/helpers.py:120-123 ------
  * A row whose fp32 sum of squares is not in (0, inf) -- all zero, a NaN or inf element, squares that overflow or underflow -- becomes an all +0.0 row. */
 int fid_l2_normalize_f16(fid_ctx *ctx, const float *emb_dev, int n, int dim, void *out_f16_dev);

@@ -105,6 +105,8 @@ class DrawStyle(C.Structure):
 MEASURE_KEYS = ("sharpness", "mean", "contrast", "clipped", "yaw", "pitch", "residual")       # words 0 .. 6 of a fid_face_measure row
 MEASURE_PIXELS_VALID, MEASURE_POSE_VALID = 1, 2                                                # stats word 7
 
+SHOT_META_WORDS = 16             # FID_SHOT_META_WORDS: stream, track id, ident_idx, ident_score, shot score, frame, rows, box[4], det score, 0 x 4
+
 
 class MeasureConfig(C.Structure):
     """fid_measure_config (include/faceid.h): what fid_face_gates_measured divides the measured sharpness (variance of the Laplacian), contrast
@@ -215,6 +217,16 @@ SIGNATURES = {
     "fid_face_measure_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fid_face_gates_measured": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fid_shot_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "fid_shot_score_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "fid_shots_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void_pp]),
+    "fid_shots_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fid_track_keep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i32_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                 C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fid_shots_flush": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "fid_shots_finished": (C.c_int, [C.c_void_p, C.c_void_p, c_i32_p, c_i32_p, c_void_pp, c_void_pp, c_void_pp]),
+    "fid_shots_clear_finished": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fid_shots_read": (C.c_int, [C.c_void_p, C.c_void_p, c_i32_p]),
     "fid_gallery_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_void_pp]),
     "fid_gallery_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "fid_gallery_info": (C.c_int, [C.c_void_p, c_int_p, c_int_p, c_int_p]),

@@ -22,17 +22,7 @@
 #include <cmath>
 
 #include "common.h"
-
-struct fid_tracker {
-    int S = 0, T = 0, device = 0;
-    int32_t *slots = nullptr;                // [S][T][FID_TRACK_SLOT_WORDS]
-    int32_t *streams = nullptr;              // [S][2] = {next_id, lost}
-    int32_t *tab = nullptr;                  // [tab_cap] stream of frame b | [tab_cap] EMBED-flagged faces of frame b
-    int tab_cap = 0;
-    bool pending = false;                    // a step whose identify has not run
-    int B = 0, cap = 0, row_cap = 0;         // ... and its shape
-    std::vector<int32_t> stream;             // ... and its stream array
-};
+#include "track_state.h"
 
 namespace {
 
@@ -388,6 +378,7 @@ int fid_track_step(fid_ctx *ctx, fid_tracker *trk, const float *det_dev, const i
                        src_dev, row_cap);
     FID_HIP(hipGetLastError());
     trk->pending = true;
+    trk->serial += 1;
     trk->B = B; trk->cap = cap; trk->row_cap = row_cap;
     trk->stream.assign(stream, stream + B);
     return FID_OK;

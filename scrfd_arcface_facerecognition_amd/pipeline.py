@@ -550,10 +550,24 @@ class TrackedFacePipeline(PackedFacePipeline):
     retry       a track WITHOUT a name is embedded every `retry` matches (default 1: every frame, so an unknown face is never worse
                 off than in PackedFacePipeline).
     rows / buckets / row_cap behave as in PackedFacePipeline, on the tracker's table; a due face that finds no row keeps what its track
-    knows and asks again after its interval (`overflow`)."""
+    knows and asks again after its interval (`overflow`).
+
+    best_shot   True (implies measure=True): match() follows identify() with fid_shot_score and fid_track_keep on the step's rows: of the
+                faces a track embeds, the one with the best measured score stays on the device -- unit embedding, aligned crop (keep_crops),
+                box, frame number -- and a track that ends becomes ONE finished record: finished() reads the records, group_finished() hands
+                their embeddings to a VectorGallery where they lie, finish_all() ends every live track (the end of a video).  An unnamed
+                track is embedded every `retry` matches (default: every frame), so the keeper normally sees a stranger's whole passage.
+                The tracker still decides WHEN a face is embedded.  `finished_cap`: finished records the device holds between two
+                finished() calls (further ones are dropped and counted); `measure_config`: _lib.MeasureConfig, the score's three
+                normalisations (UNCALIBRATED defaults).  reset() needs no extra call: the next step's keep finishes what the reset orphaned.
+                Off (the default), nothing of this is launched or allocated."""
 
     def __init__(self, ctx: Context, det: CompiledNet, rec: CompiledNet, *, batch: int, row_cap: int, streams: int = 1, max_tracks: int = 64,
-                 iou: float = 0.3, max_age: int = 15, refresh: int = 16, retry: int = 1, **kw):
+                 iou: float = 0.3, max_age: int = 15, refresh: int = 16, retry: int = 1, best_shot: bool = False, finished_cap: int = 256,
+                 keep_crops: bool = True, measure_config=None, **kw):
+        self.best_shot = bool(best_shot)
+        if self.best_shot:
+            kw["measure"] = True
         super().__init__(ctx, det, rec, batch=batch, row_cap=row_cap, **kw)
         if det.ctx is not ctx:
             raise ValueError("TrackedFacePipeline: detector and recogniser must share one context / stream")
@@ -568,6 +582,15 @@ class TrackedFacePipeline(PackedFacePipeline):
         self.ident_score = ctx.empty((self.B, cap), np.float32)
         self._stream = np.zeros(self.B, np.int32)
         self._identified = True                               # no step is waiting for its identify()
+        self.shots, self.finished_dropped, self._names = None, 0, None
+        if self.best_shot:
+            self.mcfg = measure_config if measure_config is not None else _lib.MeasureConfig()
+            self.finished_cap, self.keep_crops = int(finished_cap), bool(keep_crops)
+            h = C.c_void_p()
+            check(ctx.lib.fid_shots_create(ctx.handle, self.streams, self.max_tracks, self.emb_dim, self.finished_cap, int(self.keep_crops),
+                                           C.byref(h)))
+            self.shots = h
+            self.shot_score = ctx.empty((self.row_cap,), np.float32)
 
     def _pack(self):
         check(self.ctx.lib.fid_track_step(self.ctx.handle, self.tracker, C.c_void_p(self.post.det.ptr), C.c_void_p(self.post.counts.ptr),
@@ -593,6 +616,83 @@ class TrackedFacePipeline(PackedFacePipeline):
             n = 0
         super().match(gallery, thresh, q=q, n=n, idx=idx, score=score)
         self.identify(n, idx, score)
+        if self.best_shot:
+            self._names = gallery.names if gallery is not None else None
+            self._keep(q)
+
+    def _keep(self, q=None):
+        """score the rows the last embed() ran and let the keeper see the step (with no row at all the keep still runs: ended tracks finish)"""
+        lib, h, n = self.ctx.lib, self.ctx.handle, self.n_run
+        if n > 0:
+            check(lib.fid_shot_score(h, C.c_void_p(self.stats.ptr), C.c_void_p(self.measures.ptr), n, C.byref(self.mcfg),
+                                     C.c_void_p(self.shot_score.ptr)))
+        check(lib.fid_track_keep(h, self.shots, self.tracker, self._stream.ctypes.data_as(_lib.c_i32_p), self.B, self.post.cap,
+                                 C.c_void_p(self.track.ptr), C.c_void_p(self.offsets.ptr), C.c_void_p(self.src.ptr), self.row_cap, n,
+                                 C.c_void_p(self.shot_score.ptr), _lib._ptr(self.q if q is None else q),
+                                 C.c_void_p(self.crops.ptr) if self.keep_crops else None, C.c_void_p(self.post.det.ptr),
+                                 C.c_void_p(self.ident_idx.ptr), C.c_void_p(self.ident_score.ptr)))
+
+    # -- finished tracks (best_shot=True) -------------------------------------------------------------
+    def _need_shots(self):
+        if self.shots is None:
+            raise RuntimeError("TrackedFacePipeline: built without best_shot=True")
+
+    def _finished_store(self):
+        """(count, meta ptr, q ptr, crops ptr) of the finished store -- fid_shots_finished: synchronises, reads 8 bytes"""
+        self._need_shots()
+        count, dropped = C.c_int32(0), C.c_int32(0)
+        meta, q, crops = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(self.ctx.lib.fid_shots_finished(self.ctx.handle, self.shots, C.byref(count), C.byref(dropped), C.byref(meta), C.byref(q),
+                                              C.byref(crops)))
+        self.finished_dropped = int(dropped.value)
+        return int(count.value), meta.value, q.value, crops.value
+
+    def _finished_records(self, n, meta_ptr, names):
+        meta = self.ctx.borrow(meta_ptr, (n, _lib.SHOT_META_WORDS), np.int32).download() if n else np.zeros((0, _lib.SHOT_META_WORDS), np.int32)
+        f32 = meta.view(np.float32)
+        return [dict(stream=int(m[0]), track_id=int(m[1]), name=names[int(m[2])] if m[2] >= 0 and names is not None else "Unknown",
+                     similarity=float(f[3]), shot_score=float(f[4]), frame=int(m[5]), rows=int(m[6]), bbox=f[7:11].copy(), det_score=float(f[11]),
+                     embedding=None, crop=None) for m, f in zip(meta, f32)]
+
+    def finished(self, clear: bool = True, names=None):
+        """The tracks that have ended since the last clear, in the order they ended: one dict each -- stream, track_id, name / similarity (the
+        track's identity as of its last embedded face; names: default the last match()'s gallery's), shot_score, frame (of the stream, counted
+        over the steps since the pipeline was built), rows (faces of the track that were embedded), bbox, det_score, embedding (unit fp16
+        [512], the bits fid_gallery_group reads) and crop (uint8 [112,112,3] BGR, None without keep_crops) of the best shot.  Synchronises.
+        `finished_dropped` says how many records found the store full."""
+        n, meta, q, crops = self._finished_store()
+        recs = self._finished_records(n, meta, self._names if names is None else names)
+        if n:
+            emb = self.ctx.borrow(q, (n, self.emb_dim), np.float16).download()
+            img = self.ctx.borrow(crops, (n, 112, 112, 3), np.uint8).download() if crops else None
+            for k, r in enumerate(recs):
+                r["embedding"], r["crop"] = emb[k].copy(), (img[k].copy() if img is not None else None)
+        if clear:
+            check(self.ctx.lib.fid_shots_clear_finished(self.ctx.handle, self.shots))
+        return recs
+
+    def finish_all(self, stream: int = -1):
+        """end every live track of one stream, or of all (-1): their best shots move to the finished store (the end of a video).  The
+        tracker is not touched: a track that goes on afterwards begins a new record."""
+        self._need_shots()
+        check(self.ctx.lib.fid_shots_flush(self.ctx.handle, self.shots, int(stream)))
+
+    def shots_state(self) -> np.ndarray:
+        """the keeper's live entries, int32 [streams, max_tracks, 16] (include/faceid.h: the meta words) -- fid_shots_read; synchronises"""
+        self._need_shots()
+        meta = np.empty((self.streams, self.max_tracks, _lib.SHOT_META_WORDS), np.int32)
+        check(self.ctx.lib.fid_shots_read(self.ctx.handle, self.shots, meta.ctypes.data_as(_lib.c_i32_p)))
+        return meta
+
+    def group_finished(self, store, ids=None, names=None, **thresholds):
+        """The finished tracks as visits: store.group_device (engine.VectorGallery) on the finished embeddings where they lie -- only the
+        count and the records' meta are read back -- then the finished store is cleared.  -> (finished records without embedding / crop,
+        group_visits' records), both in finished order.  thresholds: duplicate_threshold, grouping_threshold, similarity_threshold."""
+        n, meta, q, _ = self._finished_store()
+        recs = self._finished_records(n, meta, self._names if names is None else names)
+        groups = store.group_device(q, n, ids, **thresholds) if n else []
+        check(self.ctx.lib.fid_shots_clear_finished(self.ctx.handle, self.shots))
+        return recs, groups
 
     def run_step(self, frames_dev, H, W, gallery: Optional[Gallery], thresh: float = 0.4, stream=None):
         """One full pass over one batch of consecutive frames; stream: int [B], the camera of every frame (default: all 0), frames of one
@@ -606,7 +706,9 @@ class TrackedFacePipeline(PackedFacePipeline):
         self.match(gallery, thresh)
 
     def reset(self, stream: int = -1):
-        """forget the tracks of one stream, or of all (-1: ids start at 0 again)"""
+        """forget the tracks of one stream, or of all (-1: ids start at 0 again).  With best_shot=True the keeper is not touched here: the
+        next step's keep finishes the tracks the reset orphaned (a stream's ids begin again at 0; a track that STARTS in an orphan's slot
+        under the orphan's id still ends it)"""
         check(self.ctx.lib.fid_tracker_reset(self.ctx.handle, self.tracker, int(stream)))
         if stream < 0:
             self._identified = True
@@ -679,6 +781,9 @@ class TrackedFacePipeline(PackedFacePipeline):
         return self.rec.read(self.rec.low.outputs[0], kept).reshape(kept, -1), offsets
 
     def close(self):
+        if self.shots:
+            self.ctx.lib.fid_shots_destroy(self.ctx.handle, self.shots)
+            self.shots = None
         if self.tracker:
             self.ctx.lib.fid_tracker_destroy(self.ctx.handle, self.tracker)
             self.tracker = None

@@ -34,7 +34,8 @@ class StreamRunner:
     per-frame face lists (FacePipeline.results) in frame order.  Upload of batch i+1 overlaps compute of batch i.
     An item of the iterable may also be a `(stream_id, frame)` pair -- several cameras in one iterable, each camera's frames in time
     order --: a TrackedFacePipeline keeps the cameras' tracks apart by it (a bare frame is camera 0) and is told which frames of a ragged
-    last batch are padding, so that they age no track; any other pipeline treats every frame on its own, as before.
+    last batch are padding, so that they age no track; any other pipeline treats every frame on its own, as before.  With a pipe built
+    with best_shot=True, run() ends with `pipe.finish_all()` and `finished()` hands out the ended tracks' best shots.
     annotate=True: every step is followed by `pipe.draw` on the device (boxes, names, scores; `style`: _lib.DrawStyle), the frames are
     downloaded once per batch, and the runner yields `(faces, annotated_frame)` pairs -- the reference's output video (main.py:174-184)."""
 
@@ -101,6 +102,12 @@ class StreamRunner:
                 for r in res[:n_cur]:
                     yield r
             cur, n_cur = nxt, n_nxt
+        if self.tracked and self.pipe.best_shot:
+            self.pipe.finish_all()                                  # the video is over: every live track becomes a finished record
+
+    def finished(self, clear: bool = True):
+        """TrackedFacePipeline.finished of a pipe built with best_shot=True: the tracks that have ended, run()'s end included"""
+        return self.pipe.finished(clear=clear, names=getattr(self.gallery, "names", None))
 
     def close(self):
         for h in self.host:
