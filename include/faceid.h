@@ -594,6 +594,46 @@ int fid_topk_keys(fid_ctx *ctx, fid_gallery *g, const void *query_f16_dev, int n
                   uint64_t *keys_dev);
 int fid_topk_merge(fid_ctx *ctx, const uint64_t *keys_dev, int parts, int n, int k, int G_total, float thresh,
                    int32_t *idx_dev, float *score_dev);
+/* ---- Two-stage search: an exact int8 coarse scan for a shortlist, then the fp16 scores of the shortlist (opt-in; no default path uses it) ----
+ * What vector stores ship as "quantised search with rescoring" (Qdrant, the store behind reference qdrant_manager.py, among them), with a
+ * quantisation rule that is exact on every input, so the shortlist can be predicted to the bit.
+ * The rule, for one unit fp16 row u[0 .. dim):  m = max |u_j|.  If m == 0 or any element is NaN or inf: e = 0 and every code 0 (the row scores 0
+ * against everything and is never a candidate -- the rule of zero / deleted rows and NaN everywhere else).  Otherwise e = the smallest integer
+ * with m <= 127 * 2^e and code_j = rint(u_j * 2^-e), ties to even, an int8 in [-127, 127]; u_j * 2^-e is exact in fp32, so each element is
+ * rounded once.  Coarse score of (query q, row g) = ldexpf((float)dot_i32(code_q, code_g), e_q + e_g), exact for dim <= 1024
+ * (|dot| <= 1024 * 127 * 127 < 2^24).  The coarse path needs dim % 64 == 0 and dim <= 1024, else FID_E_INVALID.
+ * fid_quantize_rows_i8: n rows unit fp16 [n, dim] (8-byte aligned) -> codes int8 [n, dim], exps int8 [n]; asynchronous.  _host: the same on host arrays.
+ * fid_gallery_quantize: gives the gallery an int8 copy of its rows (int8 [G_padded, dim] codes + int8 [G_padded] exponents, device memory owned
+ * by the gallery, freed by fid_gallery_destroy); calling it again refreshes the copy.  fid_gallery_set_rows requantises exactly the rows it wrote,
+ * when the copy exists; a gallery that never asked for it allocates and behaves as before.  Calls that write gallery rows on the device
+ * (fid_gallery_group's NEW rows, fid_gallery_dedup's cleared rows) do NOT refresh it: call fid_gallery_quantize again after them.
+ * fid_gallery_quant_data: a read-only view of the copy (FID_E_STATE without one). */
+int fid_quantize_rows_i8(fid_ctx *ctx, const void *unit_f16_dev, int n, int dim, int8_t *codes_dev, int8_t *exps_dev);
+int fid_quantize_rows_i8_host(const uint16_t *unit_f16, int n, int dim, int8_t *codes, int8_t *exps);
+int fid_gallery_quantize(fid_ctx *ctx, fid_gallery *g);
+int fid_gallery_quant_data(fid_gallery *g, const int8_t **codes_dev, const int8_t **exps_dev);
+/* fid_coarse_keys: the int8 twin of fid_topk_keys.  Quantises the n queries (scratch arena), scans the gallery's int8 copy and writes keys_dev
+ * uint64 [n, R], 1 <= R <= FID_TOPK_MAX: per query the R best rows by COARSE score in fid_topk_keys' key format, (order-preserving bits of the
+ * coarse fp32 score << 32) | ~(first_row + row), descending, 0 = no candidate.  Only dot > 0 makes a key.  FID_E_STATE without a quantised copy.
+ * FID_TOPK_SLICES forces the slice count here too; the answer does not depend on it.
+ * fid_rerank_keys: for every non-zero key of keys_in_dev [n, R] that names a row of THIS gallery (first_row <= index < first_row + G; any other
+ * key becomes 0) the score of (query, row) is recomputed from the fp16 rows -- fp32 accumulation in a fixed order, no atomics -- and the key is
+ * rebuilt with it (0 if the score is <= 0 or NaN); keys_out_dev [n, R] (not keys_in_dev) receives each query's keys in descending order.  Its
+ * output feeds fid_topk_merge unchanged: a row-sharded gallery runs fid_coarse_keys + fid_rerank_keys on the shard that owns the rows and merges
+ * the all-gathered [parts, n, R] keys with fid_topk_merge(k = R), exactly as fid_topk_keys' output (the first k columns are the best k).  The shortlist is PER SHARD: a sharded search
+ * keeps up to parts * R candidates per query and so may find more of the exact top k than the unsharded one, never fewer.
+ * fid_gallery_search_coarse: fid_coarse_keys(first_row = 0), fid_rerank_keys, fid_topk_merge(parts = 1, k), keys in the scratch arena; needs
+ * 1 <= k <= R <= FID_TOPK_MAX.  The output contract of fid_gallery_search: all n x k entries written, strict > max(0, thresh) on the RERANKED
+ * score, (-1, 0.0) behind the last hit; FID_E_INVALID (a NULL pointer, n <= 0, k or R out of range, a NaN thresh, a dim the coarse path does not
+ * take) enqueues nothing and leaves the outputs untouched.  Asynchronous on the context's stream.
+ * NOT promised: a row whose exact score is among the k best but whose coarse score is not among the R best is missed.  Everything that IS reported
+ * carries its exact fp16 score (fp32 sums in rerank order: equal to fid_gallery_search's wherever the sums are exact, within summation-order
+ * rounding elsewhere), in the order and under the tie rule of fid_gallery_search. */
+int fid_coarse_keys(fid_ctx *ctx, fid_gallery *g, const void *query_f16_dev, int n, int R, int first_row, uint64_t *keys_dev);
+int fid_rerank_keys(fid_ctx *ctx, fid_gallery *g, const void *query_f16_dev, int n, int R, int first_row, const uint64_t *keys_in_dev,
+                    uint64_t *keys_out_dev);
+int fid_gallery_search_coarse(fid_ctx *ctx, fid_gallery *g, const void *query_f16_dev, int n, int k, int R, float thresh, int32_t *idx_dev,
+                              float *score_dev);
 /* Range search / similarity join: every (query, gallery row) with cosine >= thresh (and > 0), not the best k -- what the product layer's
  * duplicate merge asks of its vector store (reference smart_face_recognition.py:2761-2766: `search_similar(k=len(persons), threshold)`;
  * qdrant_manager.py:137-183, whose score_threshold keeps scores >= the threshold).  A zero (deleted / free) row and a NaN never hit.

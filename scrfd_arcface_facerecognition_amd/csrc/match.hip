@@ -7,11 +7,7 @@
 //       arg-max epilogue -- the n x G score matrix is never written.  First maximum wins ties and a
 //       match needs score > max(0, thresh), exactly like the strict '>' chain of the reference.
 #include "conv.h"
-
-struct fid_gallery {
-    int G = 0, Gp = 0, dim = 0;
-    void *unit_f16 = nullptr;  // [Gp][dim], rows >= G are zero
-};
+#include "gallery.h"
 
 namespace fid {
 namespace {
@@ -226,6 +222,8 @@ int fid_gallery_destroy(fid_ctx *ctx, fid_gallery *g) {
     if (!g) return FID_OK;
     if (ctx) (void)hipStreamSynchronize(ctx->stream);
     if (g->unit_f16) (void)hipFree(g->unit_f16);
+    if (g->codes_i8) (void)hipFree(g->codes_i8);
+    if (g->exps_i8) (void)hipFree(g->exps_i8);
     delete g;
     return FID_OK;
 }
@@ -323,6 +321,7 @@ int fid_gallery_set_rows(fid_ctx *ctx, fid_gallery *g, const int32_t *rows_host,
     FID_HIP(hipMemcpyAsync((char *)ws + rb, emb_host, eb, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(fid::set_rows, dim3(fid::cdiv(n, 4)), dim3(256), 0, ctx->stream, (const float *)((char *)ws + rb), (const int *)ws, n,
                        g->dim, g->G, (_Float16 *)g->unit_f16);
+    if (g->codes_i8) fid::requantize_rows(ctx, g, (const int *)ws, n);   // the int8 copy follows, where there is one (coarse.hip)
     FID_HIP(hipStreamSynchronize(ctx->stream));   // the host buffers may be reused on return
     return FID_OK;
 }

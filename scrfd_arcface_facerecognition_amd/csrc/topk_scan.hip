@@ -24,7 +24,7 @@
 #include <cmath>
 #include <cstdlib>
 
-#include "common.h"
+#include "topk_keys.h"
 
 namespace fid {
 namespace {
@@ -32,7 +32,6 @@ namespace {
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned long long u64;
 
 constexpr int TT = 128, TCK = 32;                         // tile edge (both operands), K-step
 constexpr int TMI = 4, TNI = 4;                           // fragments of a wave: 64 queries x 64 gallery rows
@@ -47,25 +46,6 @@ struct TSArgs {
     unsigned q_bytes, g_bytes;
 };
 
-__device__ __forceinline__ u64 make_key(float s, int row) {
-    const unsigned u = __float_as_uint(s);
-    return ((u64)((u & 0x80000000u) ? ~u : (u | 0x80000000u)) << 32) | (unsigned)~(unsigned)row;
-}
-__device__ __forceinline__ float key_score(u64 key) {
-    const unsigned u = (unsigned)(key >> 32);
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
-}
-// the list is sorted descending; `key` takes its place and the last entry falls out (every index static: the list stays in registers)
-template <int KP>
-__device__ __forceinline__ void list_insert(u64 (&l)[KP], u64 key) {
-#pragma unroll
-    for (int j = 0; j < KP; j++) {
-        const u64 cur = l[j];
-        const bool better = key > cur;
-        l[j] = better ? key : cur;
-        key = better ? cur : key;
-    }
-}
 __device__ __forceinline__ u64 shfl_xor_u64(u64 k, int m) {
     return ((u64)(unsigned)__shfl_xor((int)(unsigned)(k >> 32), m) << 32) | (unsigned)__shfl_xor((int)(unsigned)k, m);
 }
@@ -246,7 +226,7 @@ __global__ void __launch_bounds__(256) topk_merge(const u64 *__restrict__ keys, 
     }
 }
 
-inline int list_len(int k) { return k <= 8 ? 8 : k <= 16 ? 16 : 32; }
+}  // namespace
 
 void launch_merge(fid_ctx *ctx, const u64 *keys, int parts, long long stride_p, long long stride_q, int count, int n, int k, int G_total,
                   float thresh, u64 *keys_out, int32_t *idx, float *score) {
@@ -255,6 +235,8 @@ void launch_merge(fid_ctx *ctx, const u64 *keys, int parts, long long stride_p, 
     switch (list_len(k)) { case 8: MERGE(8); break; case 16: MERGE(16); break; default: MERGE(32); }
 #undef MERGE
 }
+
+namespace {
 
 // the scan + the merge of its lists into keys [n, k] (the context's mutex is held).  keys_out == NULL: the keys go to the front of the scratch
 // arena and *keys_arena names them (fid_gallery_search: they never leave the device's scratch).

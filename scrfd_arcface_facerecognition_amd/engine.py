@@ -261,6 +261,7 @@ class Gallery:
         gp = C.c_int()
         check(ctx.lib.fid_gallery_info(h, None, C.byref(gp), None))
         self.Gp = gp.value
+        self._quant = None              # True while the int8 copy of the coarse search (fid_gallery_quantize) is current; VectorGallery keeps it
 
     def match_device(self, q_f16_dev, n, thresh, idx_dev, score_dev):
         check(self.ctx.lib.fid_match(self.ctx.handle, self.handle, _lib._ptr(q_f16_dev), int(n), float(thresh),
@@ -322,6 +323,8 @@ class VectorGallery:
         self._free = list(range(cap - 1, old.G - 1, -1)) + self._free
         old.close()
         self._gal = new
+        if old._quant is not None:   # the int8 copy of the coarse search follows the store
+            self._quantise()
 
     def upsert(self, ids, embeddings):
         emb = np.ascontiguousarray(embeddings, dtype=np.float32).reshape(len(ids), self.dim)
@@ -349,18 +352,39 @@ class VectorGallery:
     TOPK_MAX = 32                   # FID_TOPK_MAX of include/faceid.h
     MATRIX_KS = (1, 2, 4, 5, 8)     # the k fid_gallery_topk serves
 
-    def search(self, embeddings, k: int = 5, score_threshold: float = 0.0, via: Optional[str] = None):
+    def _quantise(self):
+        """(re)build the gallery's int8 copy (fid_gallery_quantize); upsert / delete keep it current through fid_gallery_set_rows"""
+        check(self.ctx.lib.fid_gallery_quantize(self.ctx.handle, self._gal.handle))
+        self._gal._quant = True
+
+    def _quant_stale(self):
+        """a call wrote gallery rows on the device, which does not refresh the int8 copy: the next coarse search rebuilds it"""
+        if self._gal._quant:
+            self._gal._quant = False
+
+    def search(self, embeddings, k: int = 5, score_threshold: float = 0.0, via: Optional[str] = None, rerank: int = 32):
         """-> per query a list of (id, score), best first (at most k, only scores > max(0, threshold)).
         via=None: fid_gallery_topk (the score matrix in scratch) for the k it serves, the fused fid_gallery_search for every other k up to 32;
-        via="fused" / "matrix" force one of them (equal answers; which is the faster default is tools/bench_topk.py's question)."""
+        via="fused" / "matrix" force one of them (equal answers; which is the faster default is tools/bench_topk.py's question).
+        via="coarse": fid_gallery_search_coarse -- an int8 scan shortlists `rerank` rows per query (k <= rerank <= 32), which are rescored from the
+        fp16 rows.  Every reported score is the exact one; a row whose coarse score is not among the `rerank` best is missed.  The int8 copy is
+        built on first use.  Never chosen by via=None."""
         k = int(k)
-        if via not in (None, "fused", "matrix"):
-            raise ValueError("via must be None, 'fused' or 'matrix', not %r" % (via,))
+        if via not in (None, "fused", "matrix", "coarse"):
+            raise ValueError("via must be None, 'fused', 'matrix' or 'coarse', not %r" % (via,))
         if k < 1 or k > self.TOPK_MAX:
             raise ValueError("k = %d is outside 1 .. %d: range_search returns every hit at or above a threshold" % (k, self.TOPK_MAX))
         if via == "matrix" and k not in self.MATRIX_KS:
             raise ValueError("via='matrix' serves k in %s only, not %d" % (self.MATRIX_KS, k))
         fn = self.ctx.lib.fid_gallery_topk if via == "matrix" or (via is None and k in self.MATRIX_KS) else self.ctx.lib.fid_gallery_search
+        if via == "coarse":
+            rerank = int(rerank)
+            if rerank < k or rerank > self.TOPK_MAX:
+                raise ValueError("rerank = %d is outside k = %d .. %d" % (rerank, k, self.TOPK_MAX))
+            if not self._gal._quant:
+                self._quantise()
+            lib = self.ctx.lib
+            fn = lambda c, g, q, n, k, t, i, s: lib.fid_gallery_search_coarse(c, g, q, n, k, rerank, t, i, s)
         emb = np.ascontiguousarray(embeddings, dtype=np.float32).reshape(-1, self.dim)
         n = emb.shape[0]
         e = self.ctx.to_device(emb)
@@ -497,6 +521,8 @@ class VectorGallery:
         out = ctx.empty((2 * n + 2,), np.int32)
         check(ctx.lib.fid_gallery_dedup(ctx.handle, self._gal.handle, C.c_void_p(rows_dev.ptr), n, C.c_float(threshold), 1 if apply else 0,
                                         C.c_void_p(out.ptr), C.c_void_p(out.ptr + 4 * n), C.c_void_p(out.ptr + 8 * n)))
+        if apply:
+            self._quant_stale()
         got = out.download()
         return got[:n].copy(), got[n:2 * n].view(np.float32).copy(), got[2 * n:].copy()
 
@@ -527,6 +553,7 @@ class VectorGallery:
         check(ctx.lib.fid_gallery_group(ctx.handle, self._gal.handle, C.c_void_p(q_ptr), int(n), C.c_float(dup), C.c_float(group), C.c_float(search),
                                         C.c_void_p(rows_dev.ptr), len(rows), C.c_void_p(verdict.ptr), C.c_void_p(row.ptr), C.c_void_p(score.ptr),
                                         C.c_void_p(summary.ptr)))
+        self._quant_stale()
         return verdict.download(), row.download(), score.download(), summary.download()
 
     def group_device(self, q_f16_dev, n: int, ids=None, duplicate_threshold: float = 0.95, grouping_threshold: float = 0.45,
