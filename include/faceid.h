@@ -221,7 +221,10 @@ int fid_nms(fid_ctx *ctx, const float *dets_dev, int K, float iou_thres, int32_t
  * cv2.dnn.blobFromImages' layout step; reference utils/helpers.py:18-59, arcface.py:54-57.
  * For frame b and face slot f < faces_per_frame: uses kps[b, f, :] if f < counts[b], else the
  * crop is zero-filled.  crops: uint8 [B*faces_per_frame, 112,112,3] BGR.  M_dev (optional, may
- * be NULL): the 2x3 double matrices estimate_norm would return, [B*faces_per_frame, 6]. */
+ * be NULL): the 2x3 double matrices estimate_norm would return, [B*faces_per_frame, 6].
+ * A used slot whose landmarks admit no transform -- a NaN or infinite coordinate, or zero variance (five identical points) -- gets a
+ * zero crop and an M row of six NaNs (an unused slot: zero crop, zero M); the other slots of the call are not affected.  The same holds
+ * for the rows of the _ragged and _packed forms. */
 int fid_align_crops(fid_ctx *ctx, const uint8_t *frames_dev, int B, int H, int W,
                     const float *kps_dev, const int32_t *counts_dev, int cap, int faces_per_frame,
                     uint8_t *crops_dev, double *M_dev);

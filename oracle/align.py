@@ -3,9 +3,12 @@ Test infrastructure only.
 
   estimate_norm      reference utils/helpers.py:18-53 + skimage 0.18.3 _umeyama
                      (transform/_geometric.py:72-144), SURVEY.md A.2   [pinned: tests/golden/umeyama.npz]
-  warp_affine        cv2.warpAffine as called at utils/helpers.py:58, SURVEY.md A.3   [PARITY UNPINNED]
-  resize_linear      cv2.resize as called at models/scrfd.py:135, SURVEY.md A.1       [PARITY UNPINNED]
+  warp_affine        cv2.warpAffine as called at utils/helpers.py:58, SURVEY.md A.3   [PARITY UNPINNED at the LSB]
+  resize_linear      cv2.resize as called at models/scrfd.py:135, SURVEY.md A.1       [PARITY UNPINNED at the LSB]
   blob_from_images   cv2.dnn.blobFromImage(s) at scrfd.py:76-82 / arcface.py:44-50, A.4 [PARITY UNPINNED]
+
+warp_affine and resize_linear stay unpinned at the LSB (no OpenCV offline); they are bounded against float64 sampling:
+tests/test_sampling_envelope_cpu.py (geometry, centre convention, inverse, axes, border and paste position are pinned there).
 """
 import numpy as np
 
