@@ -158,6 +158,57 @@ int fid_letterbox_ragged(fid_ctx *ctx, const uint8_t *frames_dev, size_t frames_
 int fid_tile_cut(fid_ctx *ctx, const uint8_t *frames_dev, int B, int H, int W, const int32_t *tiles, int T,
                  uint8_t *out_dev, int in_h, int in_w);
 
+/* ---- NV12 video frames: what a video decoder hands out, taken as it is.  (No reference analogue: the reference's frames come from
+ * cv2.VideoCapture.read(), main.py:174-184, which converts the decoder's NV12 to BGR on the host before the reference sees a pixel.)
+ * An NV12 frame is a full-resolution Y plane and a half-resolution plane of interleaved U, V pairs, 1.5 bytes per pixel, rows `pitch`
+ * bytes apart in both planes.  B frames are ONE allocation described by fid_nv12_desc; H and W are even.
+ *
+ * The conversion is integer only and is OpenCV's COLOR_YUV2BGR_NV12, so the bytes are those a host-side cvtColor gave before.  Chroma is
+ * replicated, not interpolated: pixel (y, x) uses Y[y][x], U = UV[y>>1][(x>>1)*2], V = UV[y>>1][(x>>1)*2 + 1].  With a standard's table
+ * {CY, CUB, CUG, CVG, CVR, Y0}:
+ *   yy = max(0, Y - Y0) * CY;   u = U - 128;   v = V - 128
+ *   B = sat8((yy + CUB*u + (1 << 19)) >> 20)
+ *   G = sat8((yy + CUG*u + CVG*v + (1 << 19)) >> 20)
+ *   R = sat8((yy + CVR*v + (1 << 19)) >> 20)             >> is the arithmetic shift, sat8 clamps to 0 .. 255.
+ * Each integer is floor(c * 2^20 + 0.5) of its coefficient: BT.601 limited range 1.164, 2.018, -0.391, -0.813, 1.596 (OpenCV's own); BT.709
+ * limited range 1.164, 2.112, -0.213, -0.533, 1.793; BT.601 full range (MJPEG cameras) 1.0, 1.772, -0.344136, -0.714136, 1.402, Y0 = 0. */
+#define FID_YUV_BT601_LIMITED 0
+#define FID_YUV_BT709_LIMITED 1
+#define FID_YUV_BT601_FULL 2
+#define FID_YUV_BT601_LIMITED_TABLE {1220542, 2116026, -409993, -852492, 1673527, 16}
+#define FID_YUV_BT709_LIMITED_TABLE {1220542, 2214593, -223347, -558891, 1880097, 16}
+#define FID_YUV_BT601_FULL_TABLE {1048576, 1858077, -360853, -748826, 1470104, 0}
+typedef struct fid_nv12_desc {
+    int32_t pitch;                 /* bytes from one row to the next, in both planes; >= W */
+    int64_t uv_offset;             /* from a frame's first Y byte to its first UV byte; >= pitch * H (decoders align the plane height) */
+    int64_t frame_stride;          /* bytes from one frame to the next; >= uv_offset + pitch * H / 2 */
+    int32_t standard;              /* FID_YUV_* */
+} fid_nv12_desc;
+/* Of frame b only the bytes [b * frame_stride, b * frame_stride + uv_offset + pitch * H / 2) can be read, and of each row only its first W
+ * bytes: padding behind the last UV row, between W and pitch, between the planes and between the frames is never read.  The planes are read
+ * bytewise: pitch, uv_offset, frame_stride and the allocation need no alignment.  Validation is all-or-nothing, like the ragged calls: a NULL
+ * layout, an odd H or W, pitch < W, planes or frames that overlap (the two >= above) or an unknown standard return FID_E_INVALID with a message
+ * in fid_last_error(), and nothing is enqueued.  desc is HOST memory, read before the call returns.
+ *
+ * fid_nv12_to_bgr: nv12 -> dense uint8 [B,H,W,3] BGR on the device, one launch; B, H <= 65535.  fid_nv12_to_bgr_host: the same definition in
+ * plain loops on HOST arrays, no device involved.
+ * fid_letterbox_nv12, fid_tile_cut_nv12, fid_align_crops_nv12, fid_align_crops_packed_nv12: the arguments of their BGR namesakes with
+ * (nv12_dev, desc) in place of frames_dev.  EACH WRITES EXACTLY THE BYTES ITS NAMESAKE WRITES WHEN GIVEN fid_nv12_to_bgr OF THE SAME FRAMES
+ * (det_scale and the rows of M_dev included), with no BGR frame in device memory: every tap is converted first and interpolated second, with
+ * the namesake's own fixed-point arithmetic -- the identity copy, the exact-2x sum of four converted pixels, the zero fill outside
+ * new_w x new_h and the warp's zero for a tap outside the frame included.  The mixed-size (_ragged) forms have no NV12 twin. */
+int fid_nv12_to_bgr(fid_ctx *ctx, const uint8_t *nv12_dev, const fid_nv12_desc *desc, int B, int H, int W, uint8_t *bgr_out_dev);
+int fid_nv12_to_bgr_host(const uint8_t *nv12, const fid_nv12_desc *desc, int B, int H, int W, uint8_t *bgr_out);
+int fid_letterbox_nv12(fid_ctx *ctx, const uint8_t *nv12_dev, const fid_nv12_desc *desc, int B, int H, int W,
+                       uint8_t *out_dev, int in_h, int in_w, double *det_scale);
+int fid_tile_cut_nv12(fid_ctx *ctx, const uint8_t *nv12_dev, const fid_nv12_desc *desc, int B, int H, int W, const int32_t *tiles, int T,
+                      uint8_t *out_dev, int in_h, int in_w);
+int fid_align_crops_nv12(fid_ctx *ctx, const uint8_t *nv12_dev, const fid_nv12_desc *desc, int B, int H, int W,
+                         const float *kps_dev, const int32_t *counts_dev, int cap, int faces_per_frame,
+                         uint8_t *crops_dev, double *M_dev);
+int fid_align_crops_packed_nv12(fid_ctx *ctx, const uint8_t *nv12_dev, const fid_nv12_desc *desc, int B, int H, int W, const float *kps_dev,
+                                int cap, const int32_t *src_dev, int n_rows, uint8_t *crops_dev, double *M_dev);
+
 /* ---- SCRFD post-process: replaces the numpy code of reference models/scrfd.py:89-178,180-207
  * and utils/helpers.py:62-107 (threshold, distance2bbox/kps decode, sort, greedy NMS, max_num).
  * The 9 head tensors (scores, bbox, kps for strides 8/16/32) are given as strided views so both

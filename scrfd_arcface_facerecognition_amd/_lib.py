@@ -121,6 +121,42 @@ class MeasureConfig(C.Structure):
                          float(yaw_ratio_threshold), float(pitch_ratio_threshold))
 
 
+YUV_STANDARDS = {"bt601": 0, "bt709": 1, "bt601_full": 2}     # FID_YUV_BT601_LIMITED, FID_YUV_BT709_LIMITED, FID_YUV_BT601_FULL
+
+
+class Nv12Desc(C.Structure):
+    """fid_nv12_desc (include/faceid.h): bytes per row of both planes, bytes from a frame's first Y byte to its first UV byte, bytes from one
+    frame to the next, colour standard"""
+    _fields_ = [("pitch", C.c_int32), ("uv_offset", C.c_int64), ("frame_stride", C.c_int64), ("standard", C.c_int32)]
+
+
+def nv12_desc(H, W, pitch=None, uv_offset=None, frame_stride=None, standard="bt601") -> Nv12Desc:
+    """the layout of H x W NV12 frames; the defaults are the dense one: pitch = W, uv_offset = W*H, frame_stride = W*H*3//2"""
+    H, W = int(H), int(W)
+    pitch = W if pitch is None else int(pitch)
+    uv_offset = pitch * H if uv_offset is None else int(uv_offset)
+    frame_stride = uv_offset + pitch * (H // 2) if frame_stride is None else int(frame_stride)
+    if isinstance(standard, str):
+        if standard not in YUV_STANDARDS:
+            raise ValueError(f"unknown colour standard {standard!r}: one of {sorted(YUV_STANDARDS)}")
+        standard = YUV_STANDARDS[standard]
+    return Nv12Desc(pitch, uv_offset, frame_stride, int(standard))
+
+
+class Nv12Frames:
+    """A batch of NV12 video frames on the device, as the *_nv12 entry points take it: `buf` (a DeviceBuffer, a torch tensor or a raw device
+    pointer) holds the frames, H x W is the picture, the rest is fid_nv12_desc -- by default the dense layout ([B, H*3//2, W] uint8: H rows
+    of Y, then H/2 rows of interleaved U, V).  FacePipeline.detect / embed / run_step / draw take one wherever they take BGR frames.
+    `.args()` = the two leading arguments (nv12_dev, desc) of those entry points."""
+
+    def __init__(self, buf, H, W, pitch=None, uv_offset=None, frame_stride=None, standard="bt601"):
+        self.buf, self.H, self.W = buf, int(H), int(W)
+        self.desc = nv12_desc(H, W, pitch, uv_offset, frame_stride, standard)
+
+    def args(self):
+        return (_ptr(self.buf), C.byref(self.desc))
+
+
 def label_arrays(names, colors=None):
     """names (str or bytes per gallery row), colors (BGR triple per row, or None) as fid_labels_create / fid_draw_faces_host take them:
     (name bytes, int32 [G+1] offsets, uint8 [G,3] or None).  A str is encoded as UTF-8; the table keeps FID_LABEL_MAX bytes of it."""
@@ -175,6 +211,15 @@ SIGNATURES = {
     "fid_letterbox": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                 c_f64_p]),
     "fid_letterbox_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, c_i32_p, c_i64_p, C.c_int, C.c_void_p, C.c_int, C.c_int, c_f64_p]),
+    "fid_nv12_to_bgr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "fid_nv12_to_bgr_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "fid_letterbox_nv12": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, c_f64_p]),
+    "fid_tile_cut_nv12": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_i32_p, C.c_int, C.c_void_p, C.c_int,
+                                    C.c_int]),
+    "fid_align_crops_nv12": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_void_p]),
+    "fid_align_crops_packed_nv12": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                              C.c_int, C.c_void_p, C.c_void_p]),
     "fid_scrfd_postprocess_ragged": (C.c_int, [C.c_void_p, c_void_pp, c_i32_p, c_i32_p, c_i64_p, C.c_int, C.c_int, C.c_int, C.c_int, c_i32_p,
                                                C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "fid_align_crops_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, c_i32_p, c_i64_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,

@@ -12,8 +12,40 @@
 //
 // HBM-bound byte work: 37.6 KB written per face, <= 4 x 37.6 KB gathered from the frame (mostly L2).
 #include "common.h"
+#include "yuv_core.h"
 
 namespace {
+
+// Where a kernel's source pixels come from: load(y, x, v) gives pixel (y, x) of one image as three ints B, G, R.  The sampling arithmetic
+// below (align_face_rows, letterbox_pixel) is written once over this; it only ever asks for pixels inside the image.
+// BgrSrc: dense BGR bytes, rows `ld` pixels apart (W for a whole image, the frame's width for a rectangle of a frame).
+struct BgrSrc {
+    const uint8_t *p;
+    int ld;
+    __device__ __forceinline__ void load(int y, int x, int (&v)[3]) const {
+        const uint8_t *q = p + ((size_t)y * ld + x) * 3;
+        v[0] = q[0]; v[1] = q[1]; v[2] = q[2];
+    }
+};
+// Nv12Src: one NV12 frame (yuv_core.h), or the rectangle of it whose top-left pixel is (x0, y0): the chroma sample is the one of the
+// FRAME's 2 x 2 grid, whatever the parity of the origin.  Every tap is converted here, before anything is interpolated.
+struct Nv12Src {
+    const uint8_t *yp, *uvp;
+    int pitch, x0, y0;
+    fid_yuv_coeffs k;
+    __device__ __forceinline__ void load(int y, int x, int (&v)[3]) const { fid_nv12_pixel(k, yp, uvp, pitch, y0 + y, x0 + x, v); }
+};
+// a batch of NV12 frames as a kernel argument (fid_nv12_desc with the standard's integers resolved on the host)
+struct Nv12Batch {
+    const uint8_t *p;
+    long long frame_stride, uv_offset;
+    int pitch;
+    fid_yuv_coeffs k;
+    __device__ __forceinline__ Nv12Src frame(int b, int x0 = 0, int y0 = 0) const {
+        const uint8_t *f = p + (size_t)b * (size_t)frame_stride;
+        return Nv12Src{f, f + uv_offset, pitch, x0, y0, k};
+    }
+};
 
 __constant__ double c_template[10] = {38.2946, 51.6963, 73.5318, 51.5014, 56.0252, 71.7366, 41.5493, 92.3655, 70.7299, 92.2041};
 
@@ -29,8 +61,10 @@ constexpr int ROWS_PER_BLOCK = 16;
 
 // One block's share (ROWS_PER_BLOCK output rows from y0) of one face's crop: thread 0 estimates the transform from the landmarks `lm`
 // (NULL = no face: zero crop, zero M), every thread warps.  `src` = the face's frame, `dst` = its crop, `mo` = its row of M_out (or NULL).
-// Shared by align_warp (face slots) and align_warp_packed (dense row table): the two produce the same bytes by construction.
-__device__ __forceinline__ void align_face_rows(const uint8_t *src, int H, int W, const float *lm, uint8_t *dst, double *mo, int y0) {
+// Shared by align_warp (face slots) and align_warp_packed (dense row table): the two produce the same bytes by construction; so do their
+// NV12 forms, whose taps are converted by the source before they are weighted.
+template <class Src>
+__device__ __forceinline__ void align_face_rows(const Src &src, int H, int W, const float *lm, uint8_t *dst, double *mo, int y0) {
     const bool valid = lm != nullptr;
     __shared__ double sm[6];  // inverse map m00 m01 m02 m10 m11 m12
     __shared__ int ok;
@@ -86,10 +120,11 @@ __device__ __forceinline__ void align_face_rows(const uint8_t *src, int H, int W
         const bool x0in = ix >= 0 && ix < W, x1in = ix + 1 >= 0 && ix + 1 < W;
         const bool y0in = iy >= 0 && iy < H, y1in = iy + 1 >= 0 && iy + 1 < H;
         int acc[3] = {512, 512, 512};
-        if (y0in && x0in) { const uint8_t *q = src + ((size_t)iy * W + ix) * 3; acc[0] += w00 * q[0]; acc[1] += w00 * q[1]; acc[2] += w00 * q[2]; }
-        if (y0in && x1in) { const uint8_t *q = src + ((size_t)iy * W + ix + 1) * 3; acc[0] += w01 * q[0]; acc[1] += w01 * q[1]; acc[2] += w01 * q[2]; }
-        if (y1in && x0in) { const uint8_t *q = src + ((size_t)(iy + 1) * W + ix) * 3; acc[0] += w10 * q[0]; acc[1] += w10 * q[1]; acc[2] += w10 * q[2]; }
-        if (y1in && x1in) { const uint8_t *q = src + ((size_t)(iy + 1) * W + ix + 1) * 3; acc[0] += w11 * q[0]; acc[1] += w11 * q[1]; acc[2] += w11 * q[2]; }
+        int q[3];
+        if (y0in && x0in) { src.load(iy, ix, q); acc[0] += w00 * q[0]; acc[1] += w00 * q[1]; acc[2] += w00 * q[2]; }
+        if (y0in && x1in) { src.load(iy, ix + 1, q); acc[0] += w01 * q[0]; acc[1] += w01 * q[1]; acc[2] += w01 * q[2]; }
+        if (y1in && x0in) { src.load(iy + 1, ix, q); acc[0] += w10 * q[0]; acc[1] += w10 * q[1]; acc[2] += w10 * q[2]; }
+        if (y1in && x1in) { src.load(iy + 1, ix + 1, q); acc[0] += w11 * q[0]; acc[1] += w11 * q[1]; acc[2] += w11 * q[2]; }
         o[0] = (uint8_t)(acc[0] >> 10); o[1] = (uint8_t)(acc[1] >> 10); o[2] = (uint8_t)(acc[2] >> 10);
     }
 }
@@ -99,7 +134,16 @@ __global__ void __launch_bounds__(256) align_warp(const uint8_t *frames, int H, 
     const int slot = blockIdx.y;  // b * F + f
     const int b = slot / F, f = slot - b * F;
     const bool valid = f < counts[b] && f < cap;
-    align_face_rows(frames + (size_t)b * H * W * 3, H, W, valid ? kps + ((size_t)b * cap + f) * 10 : nullptr,
+    align_face_rows(BgrSrc{frames + (size_t)b * H * W * 3, W}, H, W, valid ? kps + ((size_t)b * cap + f) * 10 : nullptr,
+                    crops + (size_t)slot * OUT * OUT * 3, M_out ? M_out + (size_t)slot * 6 : nullptr, blockIdx.x * ROWS_PER_BLOCK);
+}
+
+__global__ void __launch_bounds__(256) align_warp_nv12(Nv12Batch nv, int H, int W, const float *kps, const int *counts,
+                                                       int cap, int F, uint8_t *crops, double *M_out) {
+    const int slot = blockIdx.y;  // b * F + f
+    const int b = slot / F, f = slot - b * F;
+    const bool valid = f < counts[b] && f < cap;
+    align_face_rows(nv.frame(b), H, W, valid ? kps + ((size_t)b * cap + f) * 10 : nullptr,
                     crops + (size_t)slot * OUT * OUT * 3, M_out ? M_out + (size_t)slot * 6 : nullptr, blockIdx.x * ROWS_PER_BLOCK);
 }
 
@@ -111,7 +155,16 @@ __global__ void __launch_bounds__(256) align_warp_packed(const uint8_t *frames, 
     const int s = src_rows[row];
     const bool valid = s >= 0 && s < B * cap;
     const int b = valid ? s / cap : 0;
-    align_face_rows(frames + (size_t)b * H * W * 3, H, W, valid ? kps + (size_t)s * 10 : nullptr,
+    align_face_rows(BgrSrc{frames + (size_t)b * H * W * 3, W}, H, W, valid ? kps + (size_t)s * 10 : nullptr,
+                    crops + (size_t)row * OUT * OUT * 3, M_out ? M_out + (size_t)row * 6 : nullptr, blockIdx.x * ROWS_PER_BLOCK);
+}
+
+__global__ void __launch_bounds__(256) align_warp_packed_nv12(Nv12Batch nv, int B, int H, int W, const float *kps, int cap,
+                                                              const int *src_rows, uint8_t *crops, double *M_out) {
+    const int row = blockIdx.y;
+    const int s = src_rows[row];
+    const bool valid = s >= 0 && s < B * cap;
+    align_face_rows(nv.frame(valid ? s / cap : 0), H, W, valid ? kps + (size_t)s * 10 : nullptr,
                     crops + (size_t)row * OUT * OUT * 3, M_out ? M_out + (size_t)row * 6 : nullptr, blockIdx.x * ROWS_PER_BLOCK);
 }
 
@@ -123,7 +176,7 @@ __global__ void __launch_bounds__(256) align_warp_ragged(const uint8_t *frames, 
     const int b = slot / F, f = slot - b * F;
     const bool valid = f < counts[b] && f < cap;
     const fid::RaggedImg g = tab[b];
-    align_face_rows(frames + g.off, g.H, g.W, valid ? kps + ((size_t)b * cap + f) * 10 : nullptr,
+    align_face_rows(BgrSrc{frames + g.off, g.W}, g.H, g.W, valid ? kps + ((size_t)b * cap + f) * 10 : nullptr,
                     crops + (size_t)slot * OUT * OUT * 3, M_out ? M_out + (size_t)slot * 6 : nullptr, blockIdx.x * ROWS_PER_BLOCK);
 }
 
@@ -133,27 +186,27 @@ __global__ void __launch_bounds__(256) align_warp_packed_ragged(const uint8_t *f
     const int s = src_rows[row];
     const bool valid = s >= 0 && s < B * cap;
     const fid::RaggedImg g = tab[valid ? s / cap : 0];
-    align_face_rows(frames + g.off, g.H, g.W, valid ? kps + (size_t)s * 10 : nullptr,
+    align_face_rows(BgrSrc{frames + g.off, g.W}, g.H, g.W, valid ? kps + (size_t)s * 10 : nullptr,
                     crops + (size_t)row * OUT * OUT * 3, M_out ? M_out + (size_t)row * 6 : nullptr, blockIdx.x * ROWS_PER_BLOCK);
 }
 
 // cv2.resize INTER_LINEAR u8 + zero letterbox paste (scrfd.py:135-138): output pixel (x, y) of one image, written to o.
-// Shared by the uniform, the mixed-size and the tile kernels: they write the same bytes by construction.  `ld` = pixels from one source row
-// to the next: W for a dense image, the frame's width for a rectangle of a frame (fid_tile_cut).
-__device__ __forceinline__ void letterbox_pixel(const uint8_t *src, int H, int W, int ld, uint8_t *o, int x, int y, int new_h, int new_w,
+// Shared by the uniform, the mixed-size and the tile kernels and their NV12 forms: they write the same bytes by construction.  `src` is the
+// H x W image (a dense image, or a rectangle of a frame for fid_tile_cut); an NV12 source converts each of the pixels asked for below.
+template <class Src>
+__device__ __forceinline__ void letterbox_pixel(const Src &src, int H, int W, uint8_t *o, int x, int y, int new_h, int new_w,
                                                 double scale_x, double scale_y, int area2x) {
     if (x >= new_w || y >= new_h) { o[0] = o[1] = o[2] = 0; return; }
+    int p00[3], p01[3], p10[3], p11[3];
     if (new_w == W && new_h == H) {
-        const uint8_t *q = src + ((size_t)y * ld + x) * 3;
-        o[0] = q[0]; o[1] = q[1]; o[2] = q[2];
+        src.load(y, x, p00);
+        o[0] = (uint8_t)p00[0]; o[1] = (uint8_t)p00[1]; o[2] = (uint8_t)p00[2];
         return;
     }
     if (area2x) {  // exact 2x decimation is INTER_AREA inside cv2.resize
-        for (int c = 0; c < 3; c++) {
-            const int s = src[((size_t)(2 * y) * ld + 2 * x) * 3 + c] + src[((size_t)(2 * y) * ld + 2 * x + 1) * 3 + c] +
-                          src[((size_t)(2 * y + 1) * ld + 2 * x) * 3 + c] + src[((size_t)(2 * y + 1) * ld + 2 * x + 1) * 3 + c];
-            o[c] = (uint8_t)((s + 2) >> 2);
-        }
+        src.load(2 * y, 2 * x, p00); src.load(2 * y, 2 * x + 1, p01);
+        src.load(2 * y + 1, 2 * x, p10); src.load(2 * y + 1, 2 * x + 1, p11);
+        for (int c = 0; c < 3; c++) o[c] = (uint8_t)((p00[c] + p01[c] + p10[c] + p11[c] + 2) >> 2);
         return;
     }
     auto coeff = [](int d, double scale, int n, int &s0, int &s1, int &a0, int &a1) {
@@ -169,12 +222,28 @@ __device__ __forceinline__ void letterbox_pixel(const uint8_t *src, int H, int W
     int sx0, sx1, a0, a1, sy0, sy1, b0, b1;
     coeff(x, scale_x, W, sx0, sx1, a0, a1);
     coeff(y, scale_y, H, sy0, sy1, b0, b1);
+    src.load(sy0, sx0, p00); src.load(sy0, sx1, p01);
+    src.load(sy1, sx0, p10); src.load(sy1, sx1, p11);
     for (int c = 0; c < 3; c++) {
-        const int T0 = src[((size_t)sy0 * ld + sx0) * 3 + c] * a0 + src[((size_t)sy0 * ld + sx1) * 3 + c] * a1;
-        const int T1 = src[((size_t)sy1 * ld + sx0) * 3 + c] * a0 + src[((size_t)sy1 * ld + sx1) * 3 + c] * a1;
+        const int T0 = p00[c] * a0 + p01[c] * a1;
+        const int T1 = p10[c] * a0 + p11[c] * a1;
         int v = (((b0 * (T0 >> 4)) >> 16) + ((b1 * (T1 >> 4)) >> 16) + 2) >> 2;
         o[c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
     }
+}
+
+// FOUR consecutive output pixels of row y through letterbox_pixel, leaving as three aligned dwords (in_w % 4 == 0, o 4-byte aligned): the same
+// bytes by construction.  For sources letterbox_pixels4 below cannot read (it fetches BGR words).  The NV12 tile cut uses it: 288 tiles of 1080p
+// frames 0.41 -> 0.29 ms, the byte stores of the native tiles being what the one-pixel kernel waits for (docs/FINDINGS.md).
+template <class Src>
+__device__ __forceinline__ void letterbox_quad(const Src &src, int H, int W, unsigned *o, int x4, int y, int new_h, int new_w, double scale_x,
+                                               double scale_y, int area2x) {
+    uint8_t px[12];
+#pragma unroll
+    for (int i = 0; i < 4; i++) letterbox_pixel(src, H, W, px + 3 * i, x4 + i, y, new_h, new_w, scale_x, scale_y, area2x);
+#pragma unroll
+    for (int j = 0; j < 3; j++)
+        o[j] = (unsigned)px[4 * j] | ((unsigned)px[4 * j + 1] << 8) | ((unsigned)px[4 * j + 2] << 16) | ((unsigned)px[4 * j + 3] << 24);
 }
 
 __global__ void __launch_bounds__(256) letterbox_kernel(const uint8_t *frames, int H, int W, uint8_t *out, int in_h, int in_w,
@@ -182,8 +251,31 @@ __global__ void __launch_bounds__(256) letterbox_kernel(const uint8_t *frames, i
     const int b = blockIdx.z;
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= in_w) return;
-    letterbox_pixel(frames + (size_t)b * H * W * 3, H, W, W, out + (((size_t)b * in_h + y) * in_w + x) * 3, x, y, new_h, new_w, scale_x, scale_y,
-                    area2x);
+    letterbox_pixel(BgrSrc{frames + (size_t)b * H * W * 3, W}, H, W, out + (((size_t)b * in_h + y) * in_w + x) * 3, x, y, new_h, new_w, scale_x,
+                    scale_y, area2x);
+}
+
+__global__ void __launch_bounds__(256) letterbox_kernel_nv12(Nv12Batch nv, int H, int W, uint8_t *out, int in_h, int in_w,
+                                                             int new_h, int new_w, double scale_x, double scale_y, int area2x) {
+    const int b = blockIdx.z;
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= in_w) return;
+    letterbox_pixel(nv.frame(b), H, W, out + (((size_t)b * in_h + y) * in_w + x) * 3, x, y, new_h, new_w, scale_x, scale_y, area2x);
+}
+
+// fid_nv12_to_bgr: two horizontally adjacent pixels per thread (they share one chroma sample), dense BGR out
+__global__ void __launch_bounds__(256) nv12_to_bgr_kernel(Nv12Batch nv, int H, int W, uint8_t *out) {
+    const int b = blockIdx.z;
+    const int x = (blockIdx.x * blockDim.x + threadIdx.x) * 2, y = blockIdx.y;
+    if (x >= W) return;
+    const Nv12Src s = nv.frame(b);
+    const uint8_t *yr = s.yp + (size_t)y * s.pitch + x, *c = s.uvp + (size_t)(y >> 1) * s.pitch + x;      // (x is even: the pair's own sample)
+    int v0[3], v1[3];
+    fid_yuv_to_bgr(s.k, yr[0], c[0], c[1], v0);
+    fid_yuv_to_bgr(s.k, yr[1], c[0], c[1], v1);
+    uint8_t *o = out + (((size_t)b * H + y) * W + x) * 3;
+    o[0] = (uint8_t)v0[0]; o[1] = (uint8_t)v0[1]; o[2] = (uint8_t)v0[2];
+    o[3] = (uint8_t)v1[0]; o[4] = (uint8_t)v1[1]; o[5] = (uint8_t)v1[2];
 }
 
 // a mixed-size batch: image blockIdx.z's geometry comes from the table; identity and exact-2x are decided per image
@@ -192,7 +284,7 @@ __global__ void __launch_bounds__(256) letterbox_kernel_ragged(const uint8_t *fr
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= in_w) return;
     const fid::RaggedImg g = tab[b];
-    letterbox_pixel(frames + g.off, g.H, g.W, g.W, out + (((size_t)b * in_h + y) * in_w + x) * 3, x, y, g.new_h, g.new_w, g.scale_x, g.scale_y,
+    letterbox_pixel(BgrSrc{frames + g.off, g.W}, g.H, g.W, out + (((size_t)b * in_h + y) * in_w + x) * 3, x, y, g.new_h, g.new_w, g.scale_x, g.scale_y,
                     g.mode == 2);
 }
 
@@ -265,7 +357,7 @@ __global__ void __launch_bounds__(256) letterbox_kernel4_ragged(const uint8_t *f
     uint8_t *o = out + (((size_t)b * in_h + y) * in_w + x4) * 3;
     if (g.mode != 0) {
         for (int i = 0; i < 4; i++)
-            letterbox_pixel(frames + g.off, g.H, g.W, g.W, o + 3 * i, x4 + i, y, g.new_h, g.new_w, g.scale_x, g.scale_y, g.mode == 2);
+            letterbox_pixel(BgrSrc{frames + g.off, g.W}, g.H, g.W, o + 3 * i, x4 + i, y, g.new_h, g.new_w, g.scale_x, g.scale_y, g.mode == 2);
         return;
     }
     letterbox_pixels4(frames, (size_t)g.off, g.H, g.W, g.W, (unsigned *)o, x4, y, g.new_h, g.new_w, g.scale_x, g.scale_y, src_bytes);
@@ -282,7 +374,27 @@ __global__ void __launch_bounds__(256) tile_cut_kernel(const uint8_t *frames, in
     const fid::TileEntry g = tab[t];
     const uint8_t *src = frames + (((size_t)g.frame * H + g.y0) * W + g.x0) * 3;
     // (kind 0: new_h x new_w == h x w, which letterbox_pixel copies 1:1 and pads with zeros)
-    letterbox_pixel(src, g.h, g.w, W, out + (((size_t)t * in_h + y) * in_w + x) * 3, x, y, g.new_h, g.new_w, g.scale_x, g.scale_y, g.mode == 2);
+    letterbox_pixel(BgrSrc{src, W}, g.h, g.w, out + (((size_t)t * in_h + y) * in_w + x) * 3, x, y, g.new_h, g.new_w, g.scale_x, g.scale_y,
+                    g.mode == 2);
+}
+
+// the same cut from NV12 frames: the rectangle's pixels are addressed in FRAME coordinates, so an odd (x0, y0) keeps the frame's chroma grid
+__global__ void __launch_bounds__(256) tile_cut_kernel_nv12(Nv12Batch nv, const fid::TileEntry *tab, uint8_t *out, int in_h, int in_w) {
+    const int t = blockIdx.z;
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= in_w) return;
+    const fid::TileEntry g = tab[t];
+    letterbox_pixel(nv.frame(g.frame, g.x0, g.y0), g.h, g.w, out + (((size_t)t * in_h + y) * in_w + x) * 3, x, y, g.new_h, g.new_w, g.scale_x,
+                    g.scale_y, g.mode == 2);
+}
+
+__global__ void __launch_bounds__(256) tile_cut_kernel4_nv12(Nv12Batch nv, const fid::TileEntry *tab, uint8_t *out, int in_h, int in_w) {
+    const int t = blockIdx.z;
+    const int x4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, y = blockIdx.y;
+    if (x4 >= in_w) return;
+    const fid::TileEntry g = tab[t];
+    letterbox_quad(nv.frame(g.frame, g.x0, g.y0), g.h, g.w, (unsigned *)(out + (((size_t)t * in_h + y) * in_w + x4) * 3), x4, y, g.new_h, g.new_w,
+                   g.scale_x, g.scale_y, g.mode == 2);
 }
 
 // four output pixels per thread as three aligned dwords (in_w % 4 == 0), like letterbox_kernel4.  The branches are block-uniform.
@@ -311,7 +423,7 @@ __global__ void __launch_bounds__(256) tile_cut_kernel4(const uint8_t *frames, i
     }
     if (g.mode != 0) {
         for (int i = 0; i < 4; i++)
-            letterbox_pixel(frames + fbase, g.h, g.w, W, o + 3 * i, x4 + i, y, g.new_h, g.new_w, g.scale_x, g.scale_y, g.mode == 2);
+            letterbox_pixel(BgrSrc{frames + fbase, W}, g.h, g.w, o + 3 * i, x4 + i, y, g.new_h, g.new_w, g.scale_x, g.scale_y, g.mode == 2);
         return;
     }
     letterbox_pixels4(frames, fbase, g.h, g.w, W, (unsigned *)o, x4, y, g.new_h, g.new_w, g.scale_x, g.scale_y, src_bytes);
@@ -334,6 +446,17 @@ int ragged_entries(const int32_t *hw, const int64_t *offsets, size_t frames_byte
         g.off = offsets[b];
         tab[b] = g;
     }
+    return FID_OK;
+}
+
+// Host half of the NV12 entry points: validate the layout (all or nothing) and resolve the standard into the kernel argument.
+int nv12_batch(const uint8_t *nv12, const fid_nv12_desc *desc, int B, int H, int W, Nv12Batch *nv) {
+    const char *why = fid_nv12_check(desc, B, H, W);
+    FID_REQUIRE(why == nullptr, "nv12: %s (B %d, %dx%d, pitch %d, uv_offset %lld, frame_stride %lld, standard %d)", why ? why : "", B, W, H,
+                desc ? desc->pitch : 0, desc ? (long long)desc->uv_offset : 0ll, desc ? (long long)desc->frame_stride : 0ll,
+                desc ? desc->standard : 0);
+    nv->p = nv12; nv->frame_stride = desc->frame_stride; nv->uv_offset = desc->uv_offset; nv->pitch = desc->pitch;
+    fid_yuv_coeffs_for(desc->standard, &nv->k);
     return FID_OK;
 }
 
@@ -476,6 +599,101 @@ int fid_align_crops_packed_ragged(fid_ctx *ctx, const uint8_t *frames_dev, size_
     FID_TRY(fid::ragged_table(ctx, host.data(), B, &tab));
     dim3 grid(OUT / ROWS_PER_BLOCK, n_rows);
     hipLaunchKernelGGL(align_warp_packed_ragged, grid, dim3(256), 0, ctx->stream, frames_dev, tab, B, kps_dev, cap, src_dev, crops_dev, M_dev);
+    FID_HIP(hipGetLastError());
+    return FID_OK;
+}
+
+// ---- NV12 frames (include/faceid.h): the conversion alone, and the four frame readers with the conversion fused into their taps ----
+int fid_nv12_to_bgr_host(const uint8_t *nv12, const fid_nv12_desc *desc, int B, int H, int W, uint8_t *bgr_out) {
+    FID_REQUIRE(nv12 && bgr_out, "NULL argument");
+    const char *why = fid_nv12_check(desc, B, H, W);
+    FID_REQUIRE(why == nullptr, "nv12: %s", why ? why : "");
+    fid_nv12_to_bgr_frames_host(nv12, desc, B, H, W, bgr_out);
+    return FID_OK;
+}
+
+int fid_nv12_to_bgr(fid_ctx *ctx, const uint8_t *nv12_dev, const fid_nv12_desc *desc, int B, int H, int W, uint8_t *bgr_out_dev) {
+    FID_REQUIRE(ctx && nv12_dev && bgr_out_dev, "NULL argument");
+    Nv12Batch nv;
+    FID_TRY(nv12_batch(nv12_dev, desc, B, H, W, &nv));
+    FID_REQUIRE(B <= 65535 && H <= 65535, "bad sizes");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
+    dim3 grid(fid::cdiv(W / 2, 256), H, B);
+    hipLaunchKernelGGL(nv12_to_bgr_kernel, grid, dim3(256), 0, ctx->stream, nv, H, W, bgr_out_dev);
+    FID_HIP(hipGetLastError());
+    return FID_OK;
+}
+
+int fid_letterbox_nv12(fid_ctx *ctx, const uint8_t *nv12_dev, const fid_nv12_desc *desc, int B, int H, int W, uint8_t *out_dev, int in_h,
+                       int in_w, double *det_scale) {
+    FID_REQUIRE(ctx && nv12_dev && out_dev, "NULL argument");
+    FID_REQUIRE(B > 0 && H > 0 && W > 0 && in_h > 0 && in_w > 0 && B <= 65535 && in_h <= 65535, "bad sizes");
+    Nv12Batch nv;
+    FID_TRY(nv12_batch(nv12_dev, desc, B, H, W, &nv));
+    fid::RaggedImg g{};                             // fid_letterbox's geometry: the same expressions in double
+    FID_REQUIRE(fid::ragged_geometry(H, W, in_h, in_w, &g), "degenerate letterbox %dx%d", g.new_w, g.new_h);
+    if (det_scale) *det_scale = (double)g.new_h / (double)H;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
+    // (one output pixel per thread: with four, 32 frames of 1080p -> 640x640 took 0.053 instead of 0.048 ms -- docs/FINDINGS.md)
+    dim3 grid(fid::cdiv(in_w, 256), in_h, B);
+    hipLaunchKernelGGL(letterbox_kernel_nv12, grid, dim3(256), 0, ctx->stream, nv, H, W, out_dev, in_h, in_w, g.new_h, g.new_w, g.scale_x,
+                       g.scale_y, g.mode == 2 ? 1 : 0);
+    FID_HIP(hipGetLastError());
+    return FID_OK;
+}
+
+int fid_tile_cut_nv12(fid_ctx *ctx, const uint8_t *nv12_dev, const fid_nv12_desc *desc, int B, int H, int W, const int32_t *tiles, int T,
+                      uint8_t *out_dev, int in_h, int in_w) {
+    FID_REQUIRE(ctx && nv12_dev && tiles && out_dev, "NULL argument");
+    FID_REQUIRE(B > 0 && H > 0 && W > 0 && in_h > 0 && in_w > 0 && T > 0 && T <= 65535 && in_h <= 65535, "bad sizes");
+    Nv12Batch nv;
+    FID_TRY(nv12_batch(nv12_dev, desc, B, H, W, &nv));
+    std::vector<fid::TileEntry> host;
+    FID_TRY(fid::tile_entries(tiles, T, B, H, W, in_h, in_w, host, nullptr));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
+    const fid::TileEntry *tab;
+    FID_TRY(fid::tile_table(ctx, host.data(), T, &tab));
+    if (in_w % 4 == 0 && ((size_t)out_dev & 3) == 0) {
+        dim3 grid4(fid::cdiv(in_w / 4, 256), in_h, T);
+        hipLaunchKernelGGL(tile_cut_kernel4_nv12, grid4, dim3(256), 0, ctx->stream, nv, tab, out_dev, in_h, in_w);
+    } else {
+        dim3 grid(fid::cdiv(in_w, 256), in_h, T);
+        hipLaunchKernelGGL(tile_cut_kernel_nv12, grid, dim3(256), 0, ctx->stream, nv, tab, out_dev, in_h, in_w);
+    }
+    FID_HIP(hipGetLastError());
+    return FID_OK;
+}
+
+int fid_align_crops_nv12(fid_ctx *ctx, const uint8_t *nv12_dev, const fid_nv12_desc *desc, int B, int H, int W, const float *kps_dev,
+                         const int32_t *counts_dev, int cap, int faces_per_frame, uint8_t *crops_dev, double *M_dev) {
+    FID_REQUIRE(ctx && nv12_dev && kps_dev && counts_dev && crops_dev, "NULL argument");
+    FID_REQUIRE(B > 0 && H > 0 && W > 0 && cap > 0 && faces_per_frame > 0, "bad sizes");
+    FID_REQUIRE((long long)B * faces_per_frame <= 65535, "too many face slots per call (%lld)", (long long)B * faces_per_frame);
+    Nv12Batch nv;
+    FID_TRY(nv12_batch(nv12_dev, desc, B, H, W, &nv));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
+    dim3 grid(OUT / ROWS_PER_BLOCK, B * faces_per_frame);
+    hipLaunchKernelGGL(align_warp_nv12, grid, dim3(256), 0, ctx->stream, nv, H, W, kps_dev, counts_dev, cap, faces_per_frame, crops_dev, M_dev);
+    FID_HIP(hipGetLastError());
+    return FID_OK;
+}
+
+int fid_align_crops_packed_nv12(fid_ctx *ctx, const uint8_t *nv12_dev, const fid_nv12_desc *desc, int B, int H, int W, const float *kps_dev,
+                                int cap, const int32_t *src_dev, int n_rows, uint8_t *crops_dev, double *M_dev) {
+    FID_REQUIRE(ctx && nv12_dev && kps_dev && src_dev && crops_dev, "NULL argument");
+    FID_REQUIRE(B > 0 && H > 0 && W > 0 && cap > 0 && n_rows > 0, "bad sizes");
+    FID_REQUIRE((long long)B * cap <= 0x7FFFFFFFll, "B * cap = %lld overflows the row table's int32 entries", (long long)B * cap);
+    FID_REQUIRE(n_rows <= 65535, "too many face rows per call (%d)", n_rows);
+    Nv12Batch nv;
+    FID_TRY(nv12_batch(nv12_dev, desc, B, H, W, &nv));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
+    dim3 grid(OUT / ROWS_PER_BLOCK, n_rows);
+    hipLaunchKernelGGL(align_warp_packed_nv12, grid, dim3(256), 0, ctx->stream, nv, B, H, W, kps_dev, cap, src_dev, crops_dev, M_dev);
     FID_HIP(hipGetLastError());
     return FID_OK;
 }

@@ -77,7 +77,21 @@ def tile_plan(H: int, W: int, in_hw, overlap: int = 128, overview: bool = True, 
     return np.array([(b,) + r for b in range(batch) for r in rows], dtype=np.int32).reshape(-1, 6)
 
 
+def frame_reader(name: str, frames, H: int, W: int):
+    """The entry point that reads `frames` and its leading arguments: BGR frames (a device buffer uint8 [B,H,W,3]) -> (name, (frames_dev,));
+    _lib.Nv12Frames -> (name + "_nv12", (nv12_dev, desc)), the twin that converts every tap on the fly and writes the same bytes."""
+    if isinstance(frames, _lib.Nv12Frames):
+        if (frames.H, frames.W) != (int(H), int(W)):
+            raise ValueError(f"Nv12Frames of {frames.W}x{frames.H} passed as {W}x{H}")
+        return name + "_nv12", frames.args()
+    return name, (_lib._ptr(frames),)
+
+
 class FacePipeline:
+    """frames_dev of detect / embed / run_step / draw: BGR uint8 [B,H,W,3] on the device, or _lib.Nv12Frames (a decoder's NV12 frames as they
+    are: the letterbox, the tile cut and the warp convert each tap, fid_*_nv12; no BGR frame is built, and every result is the one the BGR
+    path gives on fid_nv12_to_bgr of the same frames)."""
+
     def __init__(self, ctx: Context, det: CompiledNet, rec: CompiledNet, *, batch: int, faces_per_frame: int = 1,
                  conf_thres: float = 0.5, iou_thres: float = 0.4, metric: int = 0, det_cap: int = 256,
                  q_buffer=None, tiling=None):
@@ -96,6 +110,7 @@ class FacePipeline:
         self.score = ctx.empty((self.n_slots,), np.float32)
         self._det_in = None
         self._hv: Optional[HeadViews] = None
+        self.bgr = None                                        # draw()'s BGR frames when the input is NV12
         self._set_tiling(tiling)
 
     def _set_tiling(self, tiling):
@@ -119,7 +134,8 @@ class FacePipeline:
         assert self.det.max_batch >= T, f"tiling: {T} tiles per step exceed the detector's max_batch {self.det.max_batch}"
         if self._tile_buf is None or self._tile_buf.shape[0] < T:
             self._tile_buf = ctx.empty((T, in_h, in_w, 3), np.uint8)
-        check(ctx.lib.fid_tile_cut(ctx.handle, _lib._ptr(frames_dev), self.B, H, W, tiles.ctypes.data_as(_lib.c_i32_p), T,
+        fn, lead = frame_reader("fid_tile_cut", frames_dev, H, W)
+        check(getattr(ctx.lib, fn)(ctx.handle, *lead, self.B, H, W, tiles.ctypes.data_as(_lib.c_i32_p), T,
                                    C.c_void_p(self._tile_buf.ptr), in_h, in_w))
         self.det.run_device(self._tile_buf, T)
         if self._hv is None:
@@ -130,14 +146,15 @@ class FacePipeline:
         if self.tiling is not None:
             return self._detect_tiled(frames_dev, H, W)
         in_h, in_w = self.in_hw
-        if (H, W) == (in_h, in_w):
+        fn, lead = frame_reader("fid_letterbox", frames_dev, H, W)
+        if (H, W) == (in_h, in_w) and fn == "fid_letterbox":
             det_in = frames_dev
-        else:
+        else:                                                 # (NV12 frames of the detector's own size: the letterbox's identity path converts them)
             if self._det_in is None:
                 self._det_in = self.det.ctx.empty((self.B, in_h, in_w, 3), np.uint8)
             sc = C.c_double()
-            check(self.det.ctx.lib.fid_letterbox(self.det.ctx.handle, _lib._ptr(frames_dev), self.B, H, W,
-                                                 C.c_void_p(self._det_in.ptr), in_h, in_w, C.byref(sc)))
+            check(getattr(self.det.ctx.lib, fn)(self.det.ctx.handle, *lead, self.B, H, W,
+                                                C.c_void_p(self._det_in.ptr), in_h, in_w, C.byref(sc)))
             det_in = self._det_in
         self.det.run_device(det_in, self.B)
         if self._hv is None:
@@ -145,9 +162,10 @@ class FacePipeline:
         self.post.run(self._hv, self.B, self.in_hw, (H, W), self.conf, self.iou, self.F, self.metric)
 
     def embed(self, frames_dev, H, W):
-        check(self.ctx.lib.fid_align_crops(self.ctx.handle, _lib._ptr(frames_dev), self.B, H, W,
-                                           C.c_void_p(self.post.kps.ptr), C.c_void_p(self.post.counts.ptr),
-                                           self.post.cap, self.F, C.c_void_p(self.crops.ptr), None))
+        fn, lead = frame_reader("fid_align_crops", frames_dev, H, W)
+        check(getattr(self.ctx.lib, fn)(self.ctx.handle, *lead, self.B, H, W,
+                                        C.c_void_p(self.post.kps.ptr), C.c_void_p(self.post.counts.ptr),
+                                        self.post.cap, self.F, C.c_void_p(self.crops.ptr), None))
         self.rec.run_device(self.crops, self.n_slots)
         emb_ptr, _, _ = self.rec.tensor(self.rec.low.outputs[0])
         # empty face slots (f >= counts[b]) become zero rows marked by -0.0 in element 0: they never match, and the matrix the all-gather
@@ -199,16 +217,25 @@ class FacePipeline:
 
     def _draw(self, frames_dev, H, W, labels, style, idx, score, id_stride, offsets=None, n_rows=0, track=None):
         style = style if style is not None else _lib.DrawStyle()
+        if isinstance(frames_dev, _lib.Nv12Frames):           # the overlay needs BGR pixels: convert into the pipeline's own buffer, draw there
+            _, lead = frame_reader("fid_nv12_to_bgr", frames_dev, H, W)
+            if self.bgr is None or self.bgr.shape != (self.B, int(H), int(W), 3):
+                self.bgr = self.ctx.empty((self.B, int(H), int(W), 3), np.uint8)
+            check(self.ctx.lib.fid_nv12_to_bgr(self.ctx.handle, *lead, self.B, int(H), int(W), C.c_void_p(self.bgr.ptr)))
+            frames_dev = self.bgr
         check(self.ctx.lib.fid_draw_faces(self.ctx.handle, _lib._ptr(frames_dev), self.B, int(H), int(W), C.c_void_p(self.post.det.ptr),
                                           C.c_void_p(self.post.counts.ptr), self.post.cap, _lib._ptr(idx), _lib._ptr(score), int(id_stride),
                                           _lib._ptr(offsets), int(n_rows), _lib._ptr(track), self._label_handle(labels), C.byref(style)))
+        return frames_dev
 
     def draw(self, frames_dev, H, W, labels, style=None):
         """Draw the last step's boxes, names and scores onto frames_dev uint8 [B,H,W,3], in place and on the device (fid_draw_faces): what
         frame_processor does with cv2 per face (main.py:132-148).  Enqueued behind the match; nothing is read back.  Call it after the
         step's last reader of the clean frames (run_step), and before the buffer is handed back to an upload.
-        labels: a LabelTable, a Gallery, or None; style: _lib.DrawStyle (default: the reference's look)."""
-        self._draw(frames_dev, H, W, labels, style, self.idx, self.score, self.F)
+        labels: a LabelTable, a Gallery, or None; style: _lib.DrawStyle (default: the reference's look).
+        Returns the buffer that was drawn on: frames_dev itself, or -- for _lib.Nv12Frames, which are left untouched -- the pipeline's own BGR
+        buffer `self.bgr` [B,H,W,3], filled by fid_nv12_to_bgr just before (overwritten by the next draw)."""
+        return self._draw(frames_dev, H, W, labels, style, self.idx, self.score, self.F)
 
     # -- results -----------------------------------------------------------------------------------
     def results(self, gallery: Gallery):
@@ -268,9 +295,10 @@ class GroupedFacePipeline(FacePipeline):
             raise RuntimeError("GroupedFacePipeline.collect: the group is full -- embed_collected() / flush() it first")
         self.post = self.posts[k]
         self.detect(frames_dev, H, W)
-        check(self.ctx.lib.fid_align_crops(self.ctx.handle, _lib._ptr(frames_dev), self.B, H, W,
-                                           C.c_void_p(self.post.kps.ptr), C.c_void_p(self.post.counts.ptr),
-                                           self.post.cap, self.F, C.c_void_p(self.crops.ptr + k * n * 112 * 112 * 3), None))
+        fn, lead = frame_reader("fid_align_crops", frames_dev, H, W)
+        check(getattr(self.ctx.lib, fn)(self.ctx.handle, *lead, self.B, H, W,
+                                        C.c_void_p(self.post.kps.ptr), C.c_void_p(self.post.counts.ptr),
+                                        self.post.cap, self.F, C.c_void_p(self.crops.ptr + k * n * 112 * 112 * 3), None))
         self.k += 1
         return self.k == self.group
 
@@ -410,6 +438,7 @@ class PackedFacePipeline(FacePipeline):
             self.measures = ctx.empty((self.row_cap, 8), np.float32)
         self._det_in = None
         self._hv: Optional[HeadViews] = None
+        self.bgr = None
         self._set_tiling(tiling)                              # (FacePipeline: detect() tiles every frame when set)
         self.n_run = 0                                        # rows the last embed() ran
         self.rec_steps = 0                                    # recogniser runs so far (a step without a face adds none in rows="count")
@@ -435,8 +464,9 @@ class PackedFacePipeline(FacePipeline):
         else:
             self.n_run = self.row_cap
         n = self.n_run
-        check(lib.fid_align_crops_packed(h, _lib._ptr(frames_dev), self.B, H, W, C.c_void_p(self.post.kps.ptr), self.post.cap,
-                                         C.c_void_p(self.src.ptr), n, C.c_void_p(self.crops.ptr), C.c_void_p(self.M.ptr) if self.measure else None))
+        fn, lead = frame_reader("fid_align_crops_packed", frames_dev, H, W)
+        check(getattr(lib, fn)(h, *lead, self.B, H, W, C.c_void_p(self.post.kps.ptr), self.post.cap,
+                               C.c_void_p(self.src.ptr), n, C.c_void_p(self.crops.ptr), C.c_void_p(self.M.ptr) if self.measure else None))
         if self.measure:
             check(lib.fid_face_measure(h, C.c_void_p(self.crops.ptr), n, C.c_void_p(self.post.kps.ptr), C.c_void_p(self.src.ptr),
                                        C.c_void_p(self.M.ptr), C.c_void_p(self.stats.ptr), C.c_void_p(self.measures.ptr)))
@@ -456,9 +486,10 @@ class PackedFacePipeline(FacePipeline):
         self.detect(frames_dev, H, W)
         lib, h = self.ctx.lib, self.ctx.handle
         PackedFacePipeline._pack(self)                        # (every face, whatever table a subclass's steps build)
+        fn, lead = frame_reader("fid_align_crops_packed", frames_dev, H, W)
         for n in (self.buckets if self.rows == "count" else [self.row_cap]):
-            check(lib.fid_align_crops_packed(h, _lib._ptr(frames_dev), self.B, H, W, C.c_void_p(self.post.kps.ptr), self.post.cap,
-                                             C.c_void_p(self.src.ptr), n, C.c_void_p(self.crops.ptr), None))
+            check(getattr(lib, fn)(h, *lead, self.B, H, W, C.c_void_p(self.post.kps.ptr), self.post.cap,
+                                   C.c_void_p(self.src.ptr), n, C.c_void_p(self.crops.ptr), None))
             self.rec.run_device(self.crops, n)
             emb_ptr, _, _ = self.rec.tensor(self.rec.low.outputs[0])
             check(lib.fid_l2_normalize_f16_packed(h, C.c_void_p(emb_ptr), n, self.emb_dim, C.c_void_p(self.src.ptr), _lib._ptr(self.q)))
@@ -468,7 +499,7 @@ class PackedFacePipeline(FacePipeline):
 
     def draw(self, frames_dev, H, W, labels, style=None):
         """FacePipeline.draw on the row table: face f of frame b is row offsets[b] + f; only the rows the last step ran carry an identity"""
-        self._draw(frames_dev, H, W, labels, style, self.idx, self.score, 0, offsets=self.offsets, n_rows=min(self.n_run, self.row_cap))
+        return self._draw(frames_dev, H, W, labels, style, self.idx, self.score, 0, offsets=self.offsets, n_rows=min(self.n_run, self.row_cap))
 
     # -- results -----------------------------------------------------------------------------------
     def _download(self):
@@ -731,7 +762,7 @@ class TrackedFacePipeline(PackedFacePipeline):
         """FacePipeline.draw for EVERY detection, with its track's name and score; a style with the DRAW_TRACK_ID flag prints the track id"""
         if not self._identified:
             raise RuntimeError("TrackedFacePipeline: the last step has not been identified (match() / identify())")
-        self._draw(frames_dev, H, W, labels, style, self.ident_idx, self.ident_score, self.post.cap, track=self.track)
+        return self._draw(frames_dev, H, W, labels, style, self.ident_idx, self.ident_score, self.post.cap, track=self.track)
 
     # -- results -----------------------------------------------------------------------------------
     def results_tracked(self, gallery: Optional[Gallery] = None):

@@ -221,3 +221,23 @@ def draw_bbox_info(frame, bbox, similarity, name, color):
     x1, y1, _, _ = map(int, bbox)
     cv2.putText(frame, f"{name}: {similarity:.2f}", (x1, y1 - 10), cv2.FONT_HERSHEY_SIMPLEX, 1, color, 2)
     draw_bbox(frame, bbox, color)
+
+
+# ---- NV12 -> BGR on the host (no reference analogue: cv2.VideoCapture converts before the reference sees a frame).  fid_nv12_to_bgr_host:
+# the integer definition of include/faceid.h -- the bytes the device's fid_nv12_to_bgr and the fused *_nv12 readers see ----
+def nv12_to_bgr(nv12, H, W, standard="bt601", *, pitch=None, uv_offset=None, frame_stride=None):
+    """One NV12 frame (uint8 [H*3//2, W]: H rows of Y, then H/2 rows of interleaved U, V) or a batch of them ([B, H*3//2, W]) -> uint8
+    [H,W,3] / [B,H,W,3] BGR.  standard: "bt601" (limited range, OpenCV's COLOR_YUV2BGR_NV12), "bt709", "bt601_full".  A pitched layout is
+    given by pitch / uv_offset / frame_stride (fid_nv12_desc) with `nv12` the flat allocation of ONE frame unless frame_stride says more."""
+    from .._lib import load, nv12_desc
+    H, W = int(H), int(W)
+    buf = np.ascontiguousarray(nv12, dtype=np.uint8)
+    desc = nv12_desc(H, W, pitch, uv_offset, frame_stride, standard)
+    frame_bytes = desc.uv_offset + desc.pitch * (H // 2)
+    single = buf.ndim <= 2 and buf.size < desc.frame_stride + frame_bytes
+    B = 1 if single else (buf.size - frame_bytes) // max(int(desc.frame_stride), 1) + 1
+    if buf.size < (B - 1) * desc.frame_stride + frame_bytes:
+        raise ValueError(f"nv12_to_bgr: {buf.size} bytes cannot hold a {W}x{H} NV12 frame of {frame_bytes} bytes")
+    out = np.empty((B, H, W, 3), np.uint8)
+    check(load().fid_nv12_to_bgr_host(buf.ctypes.data_as(C.c_void_p), C.byref(desc), B, H, W, out.ctypes.data_as(C.c_void_p)))
+    return out[0] if single else out

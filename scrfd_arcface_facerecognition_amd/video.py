@@ -9,7 +9,7 @@ from typing import Iterable, Iterator, List
 
 import numpy as np
 
-from ._lib import Context, check
+from ._lib import Context, Nv12Frames, check
 from .engine import Gallery
 from .pipeline import FacePipeline, TrackedFacePipeline
 
@@ -37,16 +37,29 @@ class StreamRunner:
     last batch are padding, so that they age no track; any other pipeline treats every frame on its own, as before.  With a pipe built
     with best_shot=True, run() ends with `pipe.finish_all()` and `finished()` hands out the ended tracks' best shots.
     annotate=True: every step is followed by `pipe.draw` on the device (boxes, names, scores; `style`: _lib.DrawStyle), the frames are
-    downloaded once per batch, and the runner yields `(faces, annotated_frame)` pairs -- the reference's output video (main.py:174-184)."""
+    downloaded once per batch, and the runner yields `(faces, annotated_frame)` pairs -- the reference's output video (main.py:174-184).
+    pixel_format="nv12": the items are a decoder's NV12 frames, uint8 [H*3//2, W] (H rows of Y, then H/2 rows of interleaved U, V; H and W
+    even; `standard`: "bt601", "bt709" or "bt601_full"), staged and uploaded as they are -- half the bytes of BGR -- and read by the
+    pipeline's *_nv12 stages; no BGR frame is built unless annotate=True, which draws on (and downloads) the pipeline's converted buffer.
+    `upload_bytes` is what one step uploads."""
 
-    def __init__(self, pipe: FacePipeline, gallery: Gallery, frame_hw, similarity_thresh: float = 0.4, annotate: bool = False, style=None):
+    def __init__(self, pipe: FacePipeline, gallery: Gallery, frame_hw, similarity_thresh: float = 0.4, annotate: bool = False, style=None,
+                 pixel_format: str = "bgr", standard: str = "bt601"):
+        if pixel_format not in ("bgr", "nv12"):
+            raise ValueError(f"pixel_format must be 'bgr' or 'nv12', not {pixel_format!r}")
         self.pipe, self.gallery, self.thr = pipe, gallery, float(similarity_thresh)
         self.annotate, self.style = bool(annotate), style
         self.H, self.W = int(frame_hw[0]), int(frame_hw[1])
+        self.nv12 = pixel_format == "nv12"
+        if self.nv12 and (self.H % 2 or self.W % 2):
+            raise ValueError(f"NV12 frames have even sizes, not {self.W}x{self.H}")
         ctx = pipe.ctx
-        shape = (pipe.B, self.H, self.W, 3)
+        shape = (pipe.B, self.H * 3 // 2, self.W) if self.nv12 else (pipe.B, self.H, self.W, 3)
         self.host = [_Pinned(ctx, shape, np.uint8) for _ in range(2)]
         self.dev = [ctx.empty(shape, np.uint8) for _ in range(2)]
+        # what a step hands to the pipeline: the staging buffer itself, or the NV12 view of it (dense layout)
+        self.frames = [Nv12Frames(d, self.H, self.W, standard=standard) for d in self.dev] if self.nv12 else self.dev
+        self.upload_bytes = self.host[0].nbytes
         self.tracked = isinstance(pipe, TrackedFacePipeline)
         self.stream = [np.zeros(pipe.B, np.int32) for _ in range(2)]      # camera of every frame of a staging buffer, -1 = padding
 
@@ -73,6 +86,8 @@ class StreamRunner:
                     break
             if 0 < n < B:
                 self.host[k].array[n:] = 0          # ragged tail: black frames, their results are dropped
+                if self.nv12:
+                    self.host[k].array[n:, self.H:] = 128           # (black in NV12: Y = 0 with neutral chroma)
                 self.stream[k][n:] = -1
             return n
 
@@ -83,11 +98,11 @@ class StreamRunner:
         while n_cur:
             check(ctx.lib.fid_upload_wait_slot(ctx.handle, cur))   # compute waits for batch `cur` (no host sync)
             if self.tracked:
-                self.pipe.run_step(self.dev[cur], self.H, self.W, self.gallery, self.thr, stream=self.stream[cur].copy())
+                self.pipe.run_step(self.frames[cur], self.H, self.W, self.gallery, self.thr, stream=self.stream[cur].copy())
             else:
-                self.pipe.run_step(self.dev[cur], self.H, self.W, self.gallery, self.thr)
-            if self.annotate:
-                self.pipe.draw(self.dev[cur], self.H, self.W, self.gallery, self.style)   # the step's last reader of the clean frames has run
+                self.pipe.run_step(self.frames[cur], self.H, self.W, self.gallery, self.thr)
+            if self.annotate:                                       # the step's last reader of the clean frames has run
+                drawn_dev = self.pipe.draw(self.frames[cur], self.H, self.W, self.gallery, self.style)   # (NV12: the pipeline's BGR buffer)
             check(ctx.lib.fid_upload_release(ctx.handle, cur))     # dev[cur] is free again once this step has run
             nxt = cur ^ 1
             n_nxt = fill(nxt)                                       # host fills the other pinned buffer meanwhile
@@ -95,7 +110,7 @@ class StreamRunner:
                 self._upload(nxt)                                   # dev[nxt]'s last reader was step i-1: starts NOW, beside step i
             res = self.pipe.results(self.gallery)                   # synchronises on batch `cur`
             if self.annotate:
-                drawn = self.dev[cur].download()                    # (dev[cur]'s next upload is enqueued only after this batch has been yielded)
+                drawn = drawn_dev.download()                        # (dev[cur]'s next upload is enqueued only after this batch has been yielded)
                 for r, frame in zip(res[:n_cur], drawn):
                     yield r, frame
             else:
