@@ -209,6 +209,29 @@ int fid_align_crops_nv12(fid_ctx *ctx, const uint8_t *nv12_dev, const fid_nv12_d
 int fid_align_crops_packed_nv12(fid_ctx *ctx, const uint8_t *nv12_dev, const fid_nv12_desc *desc, int B, int H, int W, const float *kps_dev,
                                 int cap, const int32_t *src_dev, int n_rows, uint8_t *crops_dev, double *M_dev);
 
+/* ---- BGR -> NV12: the way out, for an encoder that wants the decoder's own format (the reference hands BGR frames to cv2.VideoWriter,
+ * main.py:174-184, which converts on the host).  The forward definition is integer only, like the inverse above.  With kr, kb the standard's
+ * luma weights (BT.601: 0.299, 0.114; BT.709: 0.2126, 0.0722), kg = 1 - kr - kb, and (ys, cs) = (219/255, 224/255) for the limited ranges,
+ * (1, 1) for the full range, a standard's table {YB, YG, YR, UB, UG, UR, VB, VG, VR, Y0} holds floor(c * 2^20 + 0.5) of
+ *   Y row   ys * (kb, kg, kr)
+ *   U row   cs * 0.5 * (1, -kg / (1 - kb), -kr / (1 - kb))
+ *   V row   cs * 0.5 * (-kb / (1 - kr), -kg / (1 - kr), 1)          each on (B, G, R); the U row and the V row sum to 0.
+ * Luma of pixel (B, G, R):      Y = sat8((YB*B + YG*G + YR*R + (Y0 << 20) + (1 << 19)) >> 20)
+ * Chroma of a 2 x 2 group whose four pixels sum to (SB, SG, SR), each 0 .. 1020 -- the box-filtered sample, the one the inverse replicates:
+ *                               U = sat8((UB*SB + UG*SG + UR*SR + (128 << 22) + (1 << 21)) >> 22),  V likewise with the V row.
+ * Every sum stays below 1.08e9 in magnitude (int32); every grey maps to U = V = 128 exactly.  One solid colour c: Y(c), and the (U, V) of the
+ * flat group S = 4 * c.  fid_nv12_to_bgr of fid_bgr_to_nv12 of a frame of flat 2 x 2 blocks is within 2 levels of it per channel. */
+#define FID_YUV_BT601_LIMITED_FWD_TABLE {102662, 528618, 269262, 460551, -305128, -155423, -74897, -385654, 460551, 16}
+#define FID_YUV_BT709_LIMITED_FWD_TABLE {65019, 644067, 191455, 460551, -355018, -105533, -42230, -418321, 460551, 16}
+#define FID_YUV_BT601_FULL_FWD_TABLE {119538, 615514, 313524, 524288, -347356, -176932, -85262, -439026, 524288, 0}
+/* fid_bgr_to_nv12: dense uint8 [B,H,W,3] BGR on the device -> B frames in the layout `desc` (checked like every NV12 layout above: H and W
+ * even ...), one launch; B <= 65535.  It writes the first W bytes of every Y row and of every UV row of the layout and NOTHING else: padding
+ * between W and pitch, between the planes, behind the last UV row and between the frames keeps its bytes.  The two buffers must not overlap.
+ * FID_E_INVALID, nothing enqueued: a NULL pointer, a bad layout, overlapping buffers.  fid_bgr_to_nv12_host: the same in plain loops on HOST
+ * arrays. */
+int fid_bgr_to_nv12(fid_ctx *ctx, const uint8_t *bgr_dev, int B, int H, int W, uint8_t *nv12_out_dev, const fid_nv12_desc *desc);
+int fid_bgr_to_nv12_host(const uint8_t *bgr, int B, int H, int W, uint8_t *nv12_out, const fid_nv12_desc *desc);
+
 /* ---- SCRFD post-process: replaces the numpy code of reference models/scrfd.py:89-178,180-207
  * and utils/helpers.py:62-107 (threshold, distance2bbox/kps decode, sort, greedy NMS, max_num).
  * The 9 head tensors (scores, bbox, kps for strides 8/16/32) are given as strided views so both
@@ -413,7 +436,22 @@ int fid_track_identify(fid_ctx *ctx, fid_tracker *trk, const int32_t *counts_dev
  *
  * fid_draw_faces_host: the same records and the same coverage test in plain loops on HOST arrays, no device involved: the definition the
  * device kernels are tested against, and what utils/helpers.draw_bbox / draw_bbox_info / draw_faces call.  The label table is given as the
- * arguments of fid_labels_create (name_offsets NULL: none). */
+ * arguments of fid_labels_create (name_offsets NULL: none).
+ *
+ * fid_draw_faces_nv12: the same overlay IN PLACE on NV12 frames (nv12_dev, desc: the layout of the NV12 section above), so that an annotated
+ * video leaves the device at 1.5 bytes per pixel and no BGR frame is ever built.  Face records, label text, pixel sets, draw order and the
+ * three identity forms are fid_draw_faces' own; what is defined here is how a pixel set lands on two planes, with the forward table of the
+ * layout's standard (fid_bgr_to_nv12):
+ *   Y plane    a pixel in some face's set gets Y(colour) of the HIGHEST face index whose set contains it; every other pixel is not written
+ *              (the pixels fid_draw_faces writes, exactly);
+ *   UV plane   a pair is written when at least one of the four pixels of its 2 x 2 group is in some set, and gets (U, V)(colour) -- the flat
+ *              group S = 4 * colour -- of the HIGHEST face index whose set contains ANY of the four; every other pair is not written.
+ * A chroma sample cannot be shared out among faces, so a thin line colours the whole pair it touches: the uncovered pixels of a partly
+ * covered group keep their luma and take the line's chroma.  Nothing is read from the frames; padding (between W and pitch, between the
+ * planes, behind the last UV row, between the frames) is never written.  FID_E_INVALID, nothing enqueued, the frames untouched: everything
+ * fid_draw_faces refuses, and a layout fid_nv12_check refuses (NULL, odd H or W, pitch < W, overlapping planes or frames, unknown standard).
+ * fid_draw_faces_nv12_host: the same in plain loops on HOST arrays: the faces in ascending order, each covered pixel sets its Y and the pair
+ * of its group. */
 typedef struct fid_labels fid_labels;
 typedef struct fid_draw_style {
     double proportion;             /* corner length / min(w, h), [0, 1]; a double: the reference multiplies by the Python float 0.2 */
@@ -433,6 +471,12 @@ int fid_draw_faces(fid_ctx *ctx, uint8_t *frames_dev, int B, int H, int W, const
 int fid_draw_faces_host(uint8_t *frames, int B, int H, int W, const float *det, const int32_t *counts, int cap, const int32_t *idx,
                         const float *score, int id_stride, const int32_t *offsets, int n_rows, const int32_t *track, const char *names,
                         const int32_t *name_offsets, const uint8_t *bgr, int G, const fid_draw_style *style);
+int fid_draw_faces_nv12(fid_ctx *ctx, uint8_t *nv12_dev, const fid_nv12_desc *desc, int B, int H, int W, const float *det_dev,
+                        const int32_t *counts_dev, int cap, const int32_t *idx_dev, const float *score_dev, int id_stride,
+                        const int32_t *offsets_dev, int n_rows, const int32_t *track_dev, fid_labels *labels, const fid_draw_style *style);
+int fid_draw_faces_nv12_host(uint8_t *nv12, const fid_nv12_desc *desc, int B, int H, int W, const float *det, const int32_t *counts, int cap,
+                             const int32_t *idx, const float *score, int id_stride, const int32_t *offsets, int n_rows, const int32_t *track,
+                             const char *names, const int32_t *name_offsets, const uint8_t *bgr, int G, const fid_draw_style *style);
 int fid_draw_glyphs(uint8_t *out /* [95 * 7] */);
 
 /* ---- face gates of the reference's product layer: replaces smart_face_recognition.py:1145-1216

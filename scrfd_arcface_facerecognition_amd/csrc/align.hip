@@ -278,6 +278,74 @@ __global__ void __launch_bounds__(256) nv12_to_bgr_kernel(Nv12Batch nv, int H, i
     o[3] = (uint8_t)v1[0]; o[4] = (uint8_t)v1[1]; o[5] = (uint8_t)v1[2];
 }
 
+// fid_bgr_to_nv12: a thread owns two horizontally adjacent 2 x 2 groups -- four pixels of two rows; the last thread of a row whose W is no
+// multiple of 4 owns one.  Both groups in a layout of dwords (`wide`: W % 4 == 0, every base and stride a multiple of 4): six dword loads,
+// one dword of Y per row and one dword holding both (U, V) pairs; anything else moves the same bytes one by one.  Only the first W bytes of
+// a row are ever addressed.
+struct Nv12Out {
+    uint8_t *p;
+    long long frame_stride, uv_offset;
+    int pitch;
+    fid_yuv_fwd k;
+};
+
+__global__ void __launch_bounds__(256) bgr_to_nv12_kernel(const uint8_t *__restrict__ bgr, int H, int W, int quads, int per_frame, Nv12Out o,
+                                                          int wide) {
+    const int i = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    if (i >= per_frame) return;
+    const int gy = i / quads, x = (i - gy * quads) * 4, y = gy * 2;
+    const int npx = min(4, W - x);                                     // 4 or 2
+    const uint8_t *src = bgr + (((size_t)b * H + y) * W + x) * 3;
+    uint8_t *yp = o.p + (size_t)b * (size_t)o.frame_stride + (size_t)y * o.pitch + x;
+    uint8_t *uvp = o.p + (size_t)b * (size_t)o.frame_stride + (size_t)o.uv_offset + (size_t)gy * o.pitch + x;
+    uint32_t w[2][3] = {{0u, 0u, 0u}, {0u, 0u, 0u}};                   // the 12 bytes of each row's four pixels
+    if (wide) {
+#pragma unroll
+        for (int r = 0; r < 2; r++) {
+            const uint32_t *q = (const uint32_t *)(src + (size_t)r * W * 3);
+            w[r][0] = q[0]; w[r][1] = q[1]; w[r][2] = q[2];
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 2; r++)
+#pragma unroll
+            for (int k = 0; k < 12; k++)
+                if (k < npx * 3) w[r][k >> 2] |= (uint32_t)src[(size_t)r * W * 3 + k] << (8 * (k & 3));
+    }
+    uint32_t yw[2] = {0u, 0u}, uvw = 0u;
+#pragma unroll
+    for (int g = 0; g < 2; g++) {
+        int s[3] = {0, 0, 0};
+#pragma unroll
+        for (int r = 0; r < 2; r++)
+#pragma unroll
+            for (int d = 0; d < 2; d++) {
+                int c[3];
+#pragma unroll
+                for (int ch = 0; ch < 3; ch++) {
+                    const int k = (g * 2 + d) * 3 + ch;
+                    c[ch] = (int)((w[r][k >> 2] >> (8 * (k & 3))) & 255u);
+                }
+                yw[r] |= (uint32_t)fid_yuv_luma(o.k, c[0], c[1], c[2]) << (8 * (g * 2 + d));
+                s[0] += c[0]; s[1] += c[1]; s[2] += c[2];
+            }
+        int uv[2];
+        fid_yuv_chroma(o.k, s[0], s[1], s[2], uv);
+        uvw |= ((uint32_t)uv[0] | ((uint32_t)uv[1] << 8)) << (16 * g);
+    }
+    if (wide) {
+        *(uint32_t *)yp = yw[0];
+        *(uint32_t *)(yp + o.pitch) = yw[1];
+        *(uint32_t *)uvp = uvw;
+    } else {
+        for (int k = 0; k < npx; k++) {
+            yp[k] = (uint8_t)(yw[0] >> (8 * k));
+            yp[(size_t)o.pitch + k] = (uint8_t)(yw[1] >> (8 * k));
+            uvp[k] = (uint8_t)(uvw >> (8 * k));
+        }
+    }
+}
+
 // a mixed-size batch: image blockIdx.z's geometry comes from the table; identity and exact-2x are decided per image
 __global__ void __launch_bounds__(256) letterbox_kernel_ragged(const uint8_t *frames, const fid::RaggedImg *tab, uint8_t *out, int in_h, int in_w) {
     const int b = blockIdx.z;
@@ -603,7 +671,7 @@ int fid_align_crops_packed_ragged(fid_ctx *ctx, const uint8_t *frames_dev, size_
     return FID_OK;
 }
 
-// ---- NV12 frames (include/faceid.h): the conversion alone, and the four frame readers with the conversion fused into their taps ----
+// ---- NV12 frames (include/faceid.h): the conversion alone, both ways, and the four frame readers with the conversion fused into their taps ----
 int fid_nv12_to_bgr_host(const uint8_t *nv12, const fid_nv12_desc *desc, int B, int H, int W, uint8_t *bgr_out) {
     FID_REQUIRE(nv12 && bgr_out, "NULL argument");
     const char *why = fid_nv12_check(desc, B, H, W);
@@ -621,6 +689,36 @@ int fid_nv12_to_bgr(fid_ctx *ctx, const uint8_t *nv12_dev, const fid_nv12_desc *
     FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
     dim3 grid(fid::cdiv(W / 2, 256), H, B);
     hipLaunchKernelGGL(nv12_to_bgr_kernel, grid, dim3(256), 0, ctx->stream, nv, H, W, bgr_out_dev);
+    FID_HIP(hipGetLastError());
+    return FID_OK;
+}
+
+int fid_bgr_to_nv12_host(const uint8_t *bgr, int B, int H, int W, uint8_t *nv12_out, const fid_nv12_desc *desc) {
+    FID_REQUIRE(bgr && nv12_out, "NULL argument");
+    const char *why = fid_nv12_check(desc, B, H, W);
+    FID_REQUIRE(why == nullptr, "nv12: %s", why ? why : "");
+    fid_bgr_to_nv12_frames_host(bgr, B, H, W, nv12_out, desc);
+    return FID_OK;
+}
+
+int fid_bgr_to_nv12(fid_ctx *ctx, const uint8_t *bgr_dev, int B, int H, int W, uint8_t *nv12_out_dev, const fid_nv12_desc *desc) {
+    FID_REQUIRE(ctx && bgr_dev && nv12_out_dev, "NULL argument");
+    Nv12Batch nv;
+    FID_TRY(nv12_batch(nv12_out_dev, desc, B, H, W, &nv));
+    FID_REQUIRE(B <= 65535, "bad sizes");
+    const uintptr_t in0 = (uintptr_t)bgr_dev, in1 = in0 + (size_t)B * H * W * 3, out0 = (uintptr_t)nv12_out_dev;
+    const uintptr_t out1 = out0 + (size_t)(B - 1) * (size_t)desc->frame_stride + (size_t)desc->uv_offset + (size_t)desc->pitch * (H / 2);
+    FID_REQUIRE(in1 <= out0 || out1 <= in0, "bgr_to_nv12: the BGR frames and the NV12 frames overlap");
+    const int quads = fid::cdiv(W, 4);
+    const long long per_frame = (long long)quads * (H / 2);
+    FID_REQUIRE(per_frame <= 0x7FFFFFFFll - 256, "bad sizes");
+    Nv12Out o{nv12_out_dev, desc->frame_stride, desc->uv_offset, desc->pitch, {}};
+    fid_yuv_fwd_for(desc->standard, &o.k);
+    const int wide = W % 4 == 0 && in0 % 4 == 0 && out0 % 4 == 0 && desc->pitch % 4 == 0 && desc->uv_offset % 4 == 0 && desc->frame_stride % 4 == 0;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
+    dim3 grid((unsigned)fid::cdiv64(per_frame, 256), B);
+    hipLaunchKernelGGL(bgr_to_nv12_kernel, grid, dim3(256), 0, ctx->stream, bgr_dev, H, W, quads, (int)per_frame, o, wide);
     FID_HIP(hipGetLastError());
     return FID_OK;
 }

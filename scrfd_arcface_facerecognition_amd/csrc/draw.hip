@@ -15,12 +15,19 @@
 //                  nothing is read from the frame; four covered pixels in a frame whose rows are dword-aligned are three dword stores,
 //                  anything else byte stores of the covered pixels only.
 //
+// NV12 frames (fid_draw_faces_nv12): draw_prepare as it is, then draw_paint_nv12 -- draw_paint's tiles, cull and walk, with each pixel also
+// keeping the INDEX of its last covering face.  Y: the pixel's own last face.  A chroma pair belongs to the last face that covers any of the
+// four pixels of its group, and the listed faces ascend, over the cull passes and the record chunks too: that face is the maximum of the four
+// indices.  Rows 2k and 2k+1 of a tile are 16 lanes apart in one wave, so a thread reduces its own two pixels per group and exchanges the
+// result with lane ^ 16; the even row stores the pairs.  Four covered Y bytes, or two written pairs, are one dword in a layout of dwords.
+//
 // This file must never get a fast-math flag: bar height and label digits are compared bit for bit with the host's.
 #include <cmath>
 #include <vector>
 
 #include "common.h"
 #include "draw_core.h"
+#include "draw_nv12_core.h"
 
 struct fid_labels {
     int G = 0, device = 0;
@@ -161,10 +168,142 @@ __global__ void __launch_bounds__(256) draw_paint(uint8_t *__restrict__ frames, 
     }
 }
 
+// the layout of the NV12 frames a kernel draws on (fid_nv12_desc with the standard's forward integers resolved on the host)
+struct Nv12Target {
+    uint8_t *p;
+    long long frame_stride, uv_offset;
+    int pitch, y_dwords, uv_dwords;
+    fid_yuv_fwd k;
+};
+
+// draw_paint on two planes.  The tile, the cull and the walk are draw_paint's, kept apart so that the BGR kernel stays as it is.
+__global__ void __launch_bounds__(256) draw_paint_nv12(const Nv12Target o, const int32_t *__restrict__ nb, const int4 *__restrict__ ext,
+                                                       const uint32_t *__restrict__ rec, int H, int W, int cap, int ntx, int tiles_per_frame,
+                                                       long long total_tiles, int r, int t) {
+    __shared__ uint32_t s_rec[REC_CHUNK * FID_DRAW_FACE_WORDS];
+    __shared__ int s_list[256];
+    __shared__ int s_wcount[4];
+    __shared__ uint8_t s_font[FID_DRAW_GLYPHS * 7 + 3];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    bool font_loaded = false;                // (block-uniform)
+    for (long long tile = blockIdx.x; tile < total_tiles; tile += gridDim.x) {
+        const int b = (int)(tile / tiles_per_frame), rem = (int)(tile % tiles_per_frame);
+        const int X0 = (rem % ntx) * TILE_W, Y0 = (rem / ntx) * TILE_H;
+        const int X1 = min(X0 + TILE_W - 1, W - 1), Y1 = min(Y0 + TILE_H - 1, H - 1);
+        const int px = X0 + (tid & 15) * 4, py = Y0 + (tid >> 4);
+        const int n = nb[b];
+        uint32_t col[4] = {0u, 0u, 0u, 0u};
+        int last[4] = {-1, -1, -1, -1};      // the face whose colour col[p] is; -1: not covered
+        bool touched = false;                // (block-uniform)
+        for (int f0 = 0; f0 < n; f0 += 256) {
+            const int f = f0 + tid;
+            bool hit = false;
+            if (f < n) {
+                const int4 e = ext[(size_t)b * cap + f];
+                hit = e.x <= e.z && e.x <= X1 && e.z >= X0 && e.y <= Y1 && e.w >= Y0;
+                if (hit) hit = fid_draw_touches((const fid_draw_face *)(rec + ((size_t)b * cap + f) * FID_DRAW_FACE_WORDS), X0, Y0, X1, Y1, r, t);
+            }
+            const unsigned long long m = __ballot(hit);
+            if (lane == 0) s_wcount[wave] = __popcll(m);
+            __syncthreads();
+            int base = 0, total = 0;
+#pragma unroll
+            for (int w = 0; w < 4; w++) {
+                const int c = s_wcount[w];
+                base += w < wave ? c : 0;
+                total += c;
+            }
+            if (hit) s_list[base + lanes_below(m, lane)] = f;
+            __syncthreads();
+            if (total == 0) continue;        // (block-uniform: nothing of this chunk touches the tile)
+            touched = true;
+            for (int j0 = 0; j0 < total; j0 += REC_CHUNK) {
+                const int nrec = min(REC_CHUNK, total - j0);
+                for (int i = tid; i < nrec * FID_DRAW_FACE_WORDS; i += 256) {
+                    const int j = i / FID_DRAW_FACE_WORDS, k = i - j * FID_DRAW_FACE_WORDS;
+                    s_rec[i] = rec[((size_t)b * cap + s_list[j0 + j]) * FID_DRAW_FACE_WORDS + k];
+                }
+                const bool my_text = tid < nrec && (rec[((size_t)b * cap + s_list[j0 + (tid < nrec ? tid : 0)]) * FID_DRAW_FACE_WORDS + 11] & 0xFFu) != 0u;
+                const int any_text = __syncthreads_or(my_text);
+                if (any_text && !font_loaded) {
+                    for (int i = tid; i < FID_DRAW_GLYPHS * 7; i += 256) s_font[i] = d_font[i];
+                    font_loaded = true;
+                    __syncthreads();
+                }
+                if (py <= Y1) {
+                    for (int j = 0; j < nrec; j++) {
+                        const fid_draw_face *fc = (const fid_draw_face *)(s_rec + j * FID_DRAW_FACE_WORDS);
+                        if (!fid_draw_touches(fc, px, py, px + 3, py, r, t)) continue;
+                        const uint32_t c = (uint32_t)fc->bgr[0] | ((uint32_t)fc->bgr[1] << 8) | ((uint32_t)fc->bgr[2] << 16);
+                        const int fi = s_list[j0 + j];
+#pragma unroll
+                        for (int p = 0; p < 4; p++)
+                            if (fid_draw_covers(fc, px + p, py, r, t, s_font)) { col[p] = c; last[p] = fi; }
+                    }
+                }
+                __syncthreads();             // the next chunk, pass or tile rewrites s_rec / s_list
+            }
+        }
+        if (!touched) continue;              // a tile no face touches -- most tiles -- ends here
+        // chroma: per group the face of the highest index over its four pixels -- this row's two, and the other row's from lane ^ 16.  Every
+        // lane takes part in the exchange (a row below the frame holds -1; H is even, so a group's two rows are in the frame or out together)
+        int gl[2];
+        uint32_t gc[2];
+#pragma unroll
+        for (int g = 0; g < 2; g++) {
+            const bool second = last[2 * g + 1] > last[2 * g];
+            gl[g] = second ? last[2 * g + 1] : last[2 * g];
+            gc[g] = second ? col[2 * g + 1] : col[2 * g];
+            const int ol = __shfl_xor(gl[g], 16);
+            const uint32_t oc = (uint32_t)__shfl_xor((int)gc[g], 16);
+            if (ol > gl[g]) { gl[g] = ol; gc[g] = oc; }
+        }
+        uint8_t *frame = o.p + (size_t)b * (size_t)o.frame_stride;
+        const unsigned cov = (last[0] >= 0 ? 1u : 0u) | (last[1] >= 0 ? 2u : 0u) | (last[2] >= 0 ? 4u : 0u) | (last[3] >= 0 ? 8u : 0u);
+        if (cov != 0u) {                     // (a covered pixel lies inside the frame: extents are clipped to it)
+            uint8_t *dst = frame + (size_t)py * o.pitch + px;
+            uint32_t yv = 0u;
+#pragma unroll
+            for (int p = 0; p < 4; p++)
+                yv |= (uint32_t)fid_yuv_luma(o.k, (int)(col[p] & 255u), (int)((col[p] >> 8) & 255u), (int)((col[p] >> 16) & 255u)) << (8 * p);
+            if (cov == 15u && o.y_dwords) {
+                *(uint32_t *)dst = yv;
+            } else {
+#pragma unroll
+                for (int p = 0; p < 4; p++)
+                    if (cov & (1u << p)) dst[p] = (uint8_t)(yv >> (8 * p));
+            }
+        }
+        if (((tid >> 4) & 1) == 0 && (gl[0] >= 0 || gl[1] >= 0)) {       // the even row of each pair of rows stores the group's pair
+            uint8_t *dst = frame + (size_t)o.uv_offset + (size_t)(py >> 1) * o.pitch + px;
+            uint32_t uvv = 0u;
+#pragma unroll
+            for (int g = 0; g < 2; g++) {
+                int uv[2];
+                fid_yuv_chroma(o.k, 4 * (int)(gc[g] & 255u), 4 * (int)((gc[g] >> 8) & 255u), 4 * (int)((gc[g] >> 16) & 255u), uv);
+                uvv |= ((uint32_t)uv[0] | ((uint32_t)uv[1] << 8)) << (16 * g);
+            }
+            if (gl[0] >= 0 && gl[1] >= 0 && o.uv_dwords) {
+                *(uint32_t *)dst = uvv;
+            } else {
+#pragma unroll
+                for (int g = 0; g < 2; g++)
+                    if (gl[g] >= 0) { dst[2 * g] = (uint8_t)(uvv >> (16 * g)); dst[2 * g + 1] = (uint8_t)(uvv >> (16 * g + 8)); }
+            }
+        }
+    }
+}
+
 int check_draw(const void *frames, int B, int H, int W, const void *det, const void *counts, int cap, const void *idx, const void *score,
                int id_stride, const void *offsets, int n_rows, const fid_draw_style *st) {
     const char *why = fid_draw_check(frames, B, H, W, det, counts, cap, idx, score, id_stride, offsets, n_rows, st);
     FID_REQUIRE(why == nullptr, "draw: %s", why ? why : "");
+    return FID_OK;
+}
+
+int check_nv12(const fid_nv12_desc *desc, int B, int H, int W) {
+    const char *why = fid_nv12_check(desc, B, H, W);
+    FID_REQUIRE(why == nullptr, "draw: nv12: %s", why ? why : "");
     return FID_OK;
 }
 
@@ -179,6 +318,26 @@ int make_labels(const char *names, const int32_t *name_offsets, const uint8_t *b
     tab.resize(G);
     for (int g = 0; g < G; g++)
         fid_draw_make_label(&tab[g], g, names ? names + name_offsets[g] : nullptr, name_offsets[g + 1] - name_offsets[g], bgr ? bgr + 3 * (size_t)g : nullptr);
+    return FID_OK;
+}
+
+// the first kernel of a draw call, BGR or NV12: the face tables in the context's scratch (the context's lock is held, its device is set)
+int prepare_faces(fid_ctx *ctx, int B, int H, int W, const float *det_dev, const int32_t *counts_dev, int cap, const int32_t *idx_dev,
+                  const float *score_dev, int id_stride, const int32_t *offsets_dev, int n_rows, const int32_t *track_dev, fid_labels *labels,
+                  const fid_draw_style *style, PrepArgs *out) {
+    const size_t faces = (size_t)B * cap;
+    const size_t off_ext = ((size_t)B * 4 + 15) & ~(size_t)15, off_rec = off_ext + faces * sizeof(int4);
+    void *ws;
+    FID_TRY(fid::get_scratch(ctx, 2, off_rec + faces * sizeof(fid_draw_face), &ws));
+    PrepArgs a{};
+    a.det = det_dev; a.counts = counts_dev; a.idx = idx_dev; a.score = score_dev;
+    a.offsets = idx_dev ? offsets_dev : nullptr; a.track = track_dev;
+    a.labels = labels ? labels->dev : nullptr; a.G = labels ? labels->G : 0;
+    a.B = B; a.cap = cap; a.id_stride = id_stride; a.n_rows = n_rows; a.H = H; a.W = W;
+    a.st = *style;
+    a.nb = (int32_t *)ws; a.ext = (int4 *)((char *)ws + off_ext); a.rec = (fid_draw_face *)((char *)ws + off_rec);
+    hipLaunchKernelGGL(draw_prepare, dim3((unsigned)fid::cdiv64((int64_t)faces, 256)), dim3(256), 0, ctx->stream, a);
+    *out = a;
     return FID_OK;
 }
 
@@ -227,18 +386,8 @@ int fid_draw_faces(fid_ctx *ctx, uint8_t *frames_dev, int B, int H, int W, const
     FID_TRY(check_draw(frames_dev, B, H, W, det_dev, counts_dev, cap, idx_dev, score_dev, id_stride, offsets_dev, n_rows, style));
     std::lock_guard<std::mutex> lk(ctx->mu);
     FID_HIP(hipSetDevice(ctx->device));
-    const size_t faces = (size_t)B * cap;
-    const size_t off_ext = ((size_t)B * 4 + 15) & ~(size_t)15, off_rec = off_ext + faces * sizeof(int4);
-    void *ws;
-    FID_TRY(fid::get_scratch(ctx, 2, off_rec + faces * sizeof(fid_draw_face), &ws));
     PrepArgs a{};
-    a.det = det_dev; a.counts = counts_dev; a.idx = idx_dev; a.score = score_dev;
-    a.offsets = idx_dev ? offsets_dev : nullptr; a.track = track_dev;
-    a.labels = labels ? labels->dev : nullptr; a.G = labels ? labels->G : 0;
-    a.B = B; a.cap = cap; a.id_stride = id_stride; a.n_rows = n_rows; a.H = H; a.W = W;
-    a.st = *style;
-    a.nb = (int32_t *)ws; a.ext = (int4 *)((char *)ws + off_ext); a.rec = (fid_draw_face *)((char *)ws + off_rec);
-    hipLaunchKernelGGL(draw_prepare, dim3((unsigned)fid::cdiv64((int64_t)faces, 256)), dim3(256), 0, ctx->stream, a);
+    FID_TRY(prepare_faces(ctx, B, H, W, det_dev, counts_dev, cap, idx_dev, score_dev, id_stride, offsets_dev, n_rows, track_dev, labels, style, &a));
     const int ntx = cdiv(W, TILE_W), nty = cdiv(H, TILE_H);
     const long long tiles_per_frame = (long long)ntx * nty, total = tiles_per_frame * B;      // (H * W * 3 fits int32: so does ntx * nty)
     const int grid = (int)std::min<long long>(total, MAX_GRID);
@@ -279,6 +428,62 @@ int fid_draw_faces_host(uint8_t *frames, int B, int H, int W, const float *det, 
                         uint8_t *p = img + ((size_t)y * W + x) * 3;
                         p[0] = fc.bgr[0]; p[1] = fc.bgr[1]; p[2] = fc.bgr[2];
                     }
+        }
+    }
+    return FID_OK;
+}
+
+int fid_draw_faces_nv12(fid_ctx *ctx, uint8_t *nv12_dev, const fid_nv12_desc *desc, int B, int H, int W, const float *det_dev,
+                        const int32_t *counts_dev, int cap, const int32_t *idx_dev, const float *score_dev, int id_stride,
+                        const int32_t *offsets_dev, int n_rows, const int32_t *track_dev, fid_labels *labels, const fid_draw_style *style) {
+    FID_REQUIRE(ctx, "draw: NULL context");
+    FID_TRY(check_draw(nv12_dev, B, H, W, det_dev, counts_dev, cap, idx_dev, score_dev, id_stride, offsets_dev, n_rows, style));
+    FID_TRY(check_nv12(desc, B, H, W));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    FID_HIP(hipSetDevice(ctx->device));
+    PrepArgs a{};
+    FID_TRY(prepare_faces(ctx, B, H, W, det_dev, counts_dev, cap, idx_dev, score_dev, id_stride, offsets_dev, n_rows, track_dev, labels, style, &a));
+    const int ntx = cdiv(W, TILE_W), nty = cdiv(H, TILE_H);
+    const long long tiles_per_frame = (long long)ntx * nty, total = tiles_per_frame * B;
+    const int grid = (int)std::min<long long>(total, MAX_GRID);
+    Nv12Target o{};
+    o.p = nv12_dev; o.frame_stride = desc->frame_stride; o.uv_offset = desc->uv_offset; o.pitch = desc->pitch;
+    o.y_dwords = (uintptr_t)nv12_dev % 4 == 0 && desc->pitch % 4 == 0 && desc->frame_stride % 4 == 0;
+    o.uv_dwords = o.y_dwords && desc->uv_offset % 4 == 0;
+    fid_yuv_fwd_for(desc->standard, &o.k);
+    hipLaunchKernelGGL(draw_paint_nv12, dim3(grid), dim3(256), 0, ctx->stream, o, (const int32_t *)a.nb, (const int4 *)a.ext,
+                       (const uint32_t *)a.rec, H, W, cap, ntx, (int)tiles_per_frame, total, (style->thickness - 1) / 2, style->text_scale);
+    FID_HIP(hipGetLastError());
+    return FID_OK;
+}
+
+int fid_draw_faces_nv12_host(uint8_t *nv12, const fid_nv12_desc *desc, int B, int H, int W, const float *det, const int32_t *counts, int cap,
+                             const int32_t *idx, const float *score, int id_stride, const int32_t *offsets, int n_rows, const int32_t *track,
+                             const char *names, const int32_t *name_offsets, const uint8_t *bgr, int G, const fid_draw_style *style) {
+    FID_TRY(check_draw(nv12, B, H, W, det, counts, cap, idx, score, id_stride, offsets, n_rows, style));
+    FID_TRY(check_nv12(desc, B, H, W));
+    std::vector<fid_draw_label> tab;
+    if (name_offsets) FID_TRY(make_labels(names, name_offsets, bgr, G, tab));
+    const int nG = (int)tab.size(), r = (style->thickness - 1) / 2, t = style->text_scale;
+    fid_yuv_fwd k;
+    fid_yuv_fwd_for(desc->standard, &k);
+    if (!idx) offsets = nullptr;
+    for (int b = 0; b < B; b++) {
+        int row0;
+        const int n = fid_draw_face_count(b, counts, cap, idx != nullptr, id_stride, offsets, n_rows, &row0);
+        uint8_t *yp = nv12 + (size_t)b * (size_t)desc->frame_stride;
+        for (int f = 0; f < n; f++) {          // ascending: a later face overwrites an earlier one, pixel by pixel and pair by pair
+            const size_t slot = (size_t)b * cap + f;
+            int ii = -1;
+            float sc = 0.f;
+            if (idx) {
+                const size_t i = offsets ? (size_t)row0 + f : (size_t)b * id_stride + f;
+                ii = idx[i]; sc = score[i];
+            }
+            const bool known = ii >= 0 && ii < nG;
+            fid_draw_face fc;
+            fid_draw_make_face(&fc, det + slot * 5, known ? &tab[ii] : nullptr, sc, track ? track[slot * 2] : -1, style, H, W);
+            fid_draw_face_nv12_host(&fc, k, yp, yp + desc->uv_offset, desc->pitch, r, t, h_font);
         }
     }
     return FID_OK;

@@ -111,6 +111,7 @@ class FacePipeline:
         self._det_in = None
         self._hv: Optional[HeadViews] = None
         self.bgr = None                                        # draw()'s BGR frames when the input is NV12
+        self.nv12_out, self.nv12_standard = None, "bt601"      # draw(out="nv12")'s NV12 frames when the input is BGR, and their standard
         self._set_tiling(tiling)
 
     def _set_tiling(self, tiling):
@@ -215,27 +216,42 @@ class FacePipeline:
             labels = labels.labels()
         return labels.handle
 
-    def _draw(self, frames_dev, H, W, labels, style, idx, score, id_stride, offsets=None, n_rows=0, track=None):
+    def _draw(self, frames_dev, H, W, labels, style, idx, score, id_stride, offsets=None, n_rows=0, track=None, out=None):
+        if out not in (None, "nv12"):
+            raise ValueError(f"draw: out must be None or 'nv12', not {out!r}")
         style = style if style is not None else _lib.DrawStyle()
-        if isinstance(frames_dev, _lib.Nv12Frames):           # the overlay needs BGR pixels: convert into the pipeline's own buffer, draw there
+        tail = (self.B, int(H), int(W), C.c_void_p(self.post.det.ptr), C.c_void_p(self.post.counts.ptr), self.post.cap, _lib._ptr(idx),
+                _lib._ptr(score), int(id_stride), _lib._ptr(offsets), int(n_rows), _lib._ptr(track), self._label_handle(labels), C.byref(style))
+        if isinstance(frames_dev, _lib.Nv12Frames):
             _, lead = frame_reader("fid_nv12_to_bgr", frames_dev, H, W)
+            if out == "nv12":                                  # in place on the two planes: no BGR frame anywhere
+                check(self.ctx.lib.fid_draw_faces_nv12(self.ctx.handle, *lead, *tail))
+                return frames_dev
+            # a BGR overlay needs BGR pixels: convert into the pipeline's own buffer, draw there
             if self.bgr is None or self.bgr.shape != (self.B, int(H), int(W), 3):
                 self.bgr = self.ctx.empty((self.B, int(H), int(W), 3), np.uint8)
             check(self.ctx.lib.fid_nv12_to_bgr(self.ctx.handle, *lead, self.B, int(H), int(W), C.c_void_p(self.bgr.ptr)))
             frames_dev = self.bgr
-        check(self.ctx.lib.fid_draw_faces(self.ctx.handle, _lib._ptr(frames_dev), self.B, int(H), int(W), C.c_void_p(self.post.det.ptr),
-                                          C.c_void_p(self.post.counts.ptr), self.post.cap, _lib._ptr(idx), _lib._ptr(score), int(id_stride),
-                                          _lib._ptr(offsets), int(n_rows), _lib._ptr(track), self._label_handle(labels), C.byref(style)))
+        check(self.ctx.lib.fid_draw_faces(self.ctx.handle, _lib._ptr(frames_dev), *tail))
+        if out == "nv12":                                      # BGR frames, drawn in place above: one conversion, half the bytes to download
+            if self.nv12_out is None or (self.nv12_out.H, self.nv12_out.W) != (int(H), int(W)):
+                self.nv12_out = _lib.Nv12Frames(self.ctx.empty((self.B, int(H) * 3 // 2, int(W)), np.uint8), H, W, standard=self.nv12_standard)
+            check(self.ctx.lib.fid_bgr_to_nv12(self.ctx.handle, _lib._ptr(frames_dev), self.B, int(H), int(W), *self.nv12_out.args()))
+            return self.nv12_out
         return frames_dev
 
-    def draw(self, frames_dev, H, W, labels, style=None):
+    def draw(self, frames_dev, H, W, labels, style=None, out=None):
         """Draw the last step's boxes, names and scores onto frames_dev uint8 [B,H,W,3], in place and on the device (fid_draw_faces): what
         frame_processor does with cv2 per face (main.py:132-148).  Enqueued behind the match; nothing is read back.  Call it after the
         step's last reader of the clean frames (run_step), and before the buffer is handed back to an upload.
         labels: a LabelTable, a Gallery, or None; style: _lib.DrawStyle (default: the reference's look).
-        Returns the buffer that was drawn on: frames_dev itself, or -- for _lib.Nv12Frames, which are left untouched -- the pipeline's own BGR
-        buffer `self.bgr` [B,H,W,3], filled by fid_nv12_to_bgr just before (overwritten by the next draw)."""
-        return self._draw(frames_dev, H, W, labels, style, self.idx, self.score, self.F)
+        out=None returns the BGR buffer that was drawn on: frames_dev itself, or -- for _lib.Nv12Frames, which are left untouched -- the
+        pipeline's own BGR buffer `self.bgr` [B,H,W,3], filled by fid_nv12_to_bgr just before (overwritten by the next draw).
+        out="nv12" returns _lib.Nv12Frames, what an encoder takes: _lib.Nv12Frames are drawn IN PLACE on their two planes
+        (fid_draw_faces_nv12; no BGR buffer is allocated) and returned; BGR frames are drawn in place as before and then converted once
+        (fid_bgr_to_nv12, standard `self.nv12_standard`) into the pipeline's own dense buffer `self.nv12_out` (overwritten by the next
+        draw; H and W even)."""
+        return self._draw(frames_dev, H, W, labels, style, self.idx, self.score, self.F, out=out)
 
     # -- results -----------------------------------------------------------------------------------
     def results(self, gallery: Gallery):
@@ -327,7 +343,7 @@ class GroupedFacePipeline(FacePipeline):
         if steps:
             self.match(gallery, thresh, n=steps * self.n_slots)
 
-    def draw(self, frames_dev, H, W, labels, style=None):
+    def draw(self, frames_dev, H, W, labels, style=None, out=None):
         raise ValueError("GroupedFacePipeline.draw: a step's identities exist only when its group's last step has run, after its frames "
                          "may have been overwritten; draw from results() on the host (utils.helpers.draw_faces)")
 
@@ -439,6 +455,7 @@ class PackedFacePipeline(FacePipeline):
         self._det_in = None
         self._hv: Optional[HeadViews] = None
         self.bgr = None
+        self.nv12_out, self.nv12_standard = None, "bt601"
         self._set_tiling(tiling)                              # (FacePipeline: detect() tiles every frame when set)
         self.n_run = 0                                        # rows the last embed() ran
         self.rec_steps = 0                                    # recogniser runs so far (a step without a face adds none in rows="count")
@@ -497,9 +514,10 @@ class PackedFacePipeline(FacePipeline):
                 FacePipeline.match(self, gallery, thresh, n=n)
         self.ctx.sync()
 
-    def draw(self, frames_dev, H, W, labels, style=None):
+    def draw(self, frames_dev, H, W, labels, style=None, out=None):
         """FacePipeline.draw on the row table: face f of frame b is row offsets[b] + f; only the rows the last step ran carry an identity"""
-        return self._draw(frames_dev, H, W, labels, style, self.idx, self.score, 0, offsets=self.offsets, n_rows=min(self.n_run, self.row_cap))
+        return self._draw(frames_dev, H, W, labels, style, self.idx, self.score, 0, offsets=self.offsets, n_rows=min(self.n_run, self.row_cap),
+                          out=out)
 
     # -- results -----------------------------------------------------------------------------------
     def _download(self):
@@ -758,11 +776,11 @@ class TrackedFacePipeline(PackedFacePipeline):
         total = int(self.ctx.borrow(self.offsets.ptr + 4 * self.B, (1,), np.int32).download()[0])
         return min(total, self.row_cap)
 
-    def draw(self, frames_dev, H, W, labels, style=None):
+    def draw(self, frames_dev, H, W, labels, style=None, out=None):
         """FacePipeline.draw for EVERY detection, with its track's name and score; a style with the DRAW_TRACK_ID flag prints the track id"""
         if not self._identified:
             raise RuntimeError("TrackedFacePipeline: the last step has not been identified (match() / identify())")
-        return self._draw(frames_dev, H, W, labels, style, self.ident_idx, self.ident_score, self.post.cap, track=self.track)
+        return self._draw(frames_dev, H, W, labels, style, self.ident_idx, self.ident_score, self.post.cap, track=self.track, out=out)
 
     # -- results -----------------------------------------------------------------------------------
     def results_tracked(self, gallery: Optional[Gallery] = None):

@@ -180,10 +180,8 @@ def _draw_host(image, boxes, idx=None, score=None, names=None, colors=None, trac
     return image
 
 
-def draw_faces(image, faces, colors=None, style=None):
-    """Draw one frame's face list -- an entry of `results()` / `results_tracked()`: (bbox, det_score, kps, name, similarity[, track id, ...])
-    per face -- onto `image` (uint8 [H,W,3], in place; returned) on the host, in list order (a later face shows over an earlier one).
-    colors: {name: (b, g, r)} or None (a fixed colour per name, in order of first appearance); "Unknown" is drawn in style.unknown_bgr."""
+def _face_names(faces):
+    """the label table of one face list: (names in order of first appearance, per face its row or -1 for "Unknown")"""
     names, idx = [], []
     for face in faces:
         name = face[3]
@@ -193,6 +191,14 @@ def draw_faces(image, faces, colors=None, style=None):
         if name not in names:
             names.append(name)
         idx.append(names.index(name))
+    return names, idx
+
+
+def draw_faces(image, faces, colors=None, style=None):
+    """Draw one frame's face list -- an entry of `results()` / `results_tracked()`: (bbox, det_score, kps, name, similarity[, track id, ...])
+    per face -- onto `image` (uint8 [H,W,3], in place; returned) on the host, in list order (a later face shows over an earlier one).
+    colors: {name: (b, g, r)} or None (a fixed colour per name, in order of first appearance); "Unknown" is drawn in style.unknown_bgr."""
+    names, idx = _face_names(faces)
     bgr = [colors[n] for n in names] if colors is not None and names else None
     track = [face[5] for face in faces] if faces and all(len(face) > 5 for face in faces) else None
     return _draw_host(image, [np.asarray(face[0], np.float32)[:4] for face in faces], idx, [face[4] for face in faces], names or None, bgr,
@@ -241,3 +247,57 @@ def nv12_to_bgr(nv12, H, W, standard="bt601", *, pitch=None, uv_offset=None, fra
     out = np.empty((B, H, W, 3), np.uint8)
     check(load().fid_nv12_to_bgr_host(buf.ctypes.data_as(C.c_void_p), C.byref(desc), B, H, W, out.ctypes.data_as(C.c_void_p)))
     return out[0] if single else out
+
+
+# ---- BGR -> NV12 on the host, and the overlay on NV12 frames (no reference analogue: cv2.VideoWriter converts BGR frames on the host).
+# fid_bgr_to_nv12_host / fid_draw_faces_nv12_host: the integer definitions of include/faceid.h, the bytes the device calls write ----
+def bgr_to_nv12(image_or_batch, standard="bt601", *, pitch=None, uv_offset=None, frame_stride=None):
+    """One BGR image (uint8 [H,W,3], H and W even) or a batch ([B,H,W,3]) -> NV12, the twin of nv12_to_bgr: uint8 [H*3//2, W] / [B, H*3//2, W]
+    in the dense layout; with pitch / uv_offset / frame_stride (fid_nv12_desc) the flat allocation of the pitched layout, B * frame_stride
+    bytes, whose padding is zero.  Luma per pixel, chroma the box-filtered sample of each 2 x 2 group."""
+    from .._lib import load, nv12_desc
+    img = np.ascontiguousarray(image_or_batch, dtype=np.uint8)
+    single = img.ndim == 3
+    if img.ndim not in (3, 4) or img.shape[-1] != 3:
+        raise ValueError(f"bgr_to_nv12 needs uint8 [H,W,3] or [B,H,W,3], not {img.shape}")
+    B, H, W = (1,) + img.shape[:2] if single else img.shape[:3]
+    desc = nv12_desc(H, W, pitch, uv_offset, frame_stride, standard)
+    dense = pitch is None and uv_offset is None and frame_stride is None
+    out = np.zeros(max(B * int(desc.frame_stride), 1), np.uint8)
+    check(load().fid_bgr_to_nv12_host(img.ctypes.data_as(C.c_void_p), B, H, W, out.ctypes.data_as(C.c_void_p), C.byref(desc)))
+    if not dense:
+        return out
+    out = out.reshape(B, H * 3 // 2, W)
+    return out[0] if single else out
+
+
+def draw_faces_nv12(nv12, H, W, faces, colors=None, style=None, standard="bt601"):
+    """draw_faces on one dense NV12 frame (uint8 [H*3//2, W], in place; returned): the same boxes, names and scores, painted on the Y plane
+    pixel by pixel and on the UV plane pair by pair (a pair takes the colour of the last face that covers any pixel of its 2 x 2 group)."""
+    from .._lib import DrawStyle, label_arrays, load, nv12_desc
+    H, W = int(H), int(W)
+    if getattr(nv12, "dtype", None) != np.uint8 or nv12.size != H * W * 3 // 2:
+        raise ValueError(f"drawing needs a dense uint8 [{H * 3 // 2}, {W}] NV12 frame, not {getattr(nv12, 'dtype', None)} {getattr(nv12, 'shape', None)}")
+    n = len(faces)
+    if n == 0:
+        return nv12
+    names, idx = _face_names(faces)
+    bgr = [colors[m] for m in names] if colors is not None and names else None
+    buf = nv12 if nv12.flags.c_contiguous and nv12.flags.writeable else np.ascontiguousarray(nv12)
+    det = np.zeros((n, 5), np.float32)
+    det[:, :4] = np.asarray([np.asarray(face[0], np.float32)[:4] for face in faces], np.float32).reshape(n, 4)
+    counts, idx = np.array([n], np.int32), np.ascontiguousarray(idx, np.int32)
+    score = np.ascontiguousarray([face[4] for face in faces], np.float32)
+    trk = None
+    if all(len(face) > 5 for face in faces):
+        trk = np.zeros((n, 2), np.int32)
+        trk[:, 0] = [face[5] for face in faces]
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    raw, offsets, cols = (None, None, None) if not names else label_arrays(names, bgr)
+    style = style if style is not None else DrawStyle()
+    desc = nv12_desc(H, W, standard=standard)
+    check(load().fid_draw_faces_nv12_host(p(buf), C.byref(desc), 1, H, W, p(det), p(counts), n, p(idx), p(score), n, None, 0, p(trk), raw, p(offsets),
+                                          p(cols), len(names), C.byref(style)))
+    if buf is not nv12:
+        nv12[...] = buf.reshape(nv12.shape)
+    return nv12

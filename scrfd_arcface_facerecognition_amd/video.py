@@ -41,17 +41,24 @@ class StreamRunner:
     pixel_format="nv12": the items are a decoder's NV12 frames, uint8 [H*3//2, W] (H rows of Y, then H/2 rows of interleaved U, V; H and W
     even; `standard`: "bt601", "bt709" or "bt601_full"), staged and uploaded as they are -- half the bytes of BGR -- and read by the
     pipeline's *_nv12 stages; no BGR frame is built unless annotate=True, which draws on (and downloads) the pipeline's converted buffer.
-    `upload_bytes` is what one step uploads."""
+    annotate_format="nv12" (with annotate=True): the annotated frames are yielded as NV12, uint8 [H*3//2, W] -- what an encoder takes --, half
+    the bytes to download.  NV12 items are drawn in place on the staging buffer's two planes (`pipe.draw(..., out="nv12")`: no BGR frame at
+    all; the draw follows the step's last reader, and the download precedes the enqueue of that buffer's next upload, as on the BGR
+    path); BGR items are drawn in place and converted once on the device, `standard` then being the output's standard.  H and W even.
+    `upload_bytes` is what one step uploads, `download_bytes` what one annotated step downloads (0 without annotate)."""
 
     def __init__(self, pipe: FacePipeline, gallery: Gallery, frame_hw, similarity_thresh: float = 0.4, annotate: bool = False, style=None,
-                 pixel_format: str = "bgr", standard: str = "bt601"):
+                 pixel_format: str = "bgr", standard: str = "bt601", annotate_format: str = "bgr"):
         if pixel_format not in ("bgr", "nv12"):
             raise ValueError(f"pixel_format must be 'bgr' or 'nv12', not {pixel_format!r}")
+        if annotate_format not in ("bgr", "nv12"):
+            raise ValueError(f"annotate_format must be 'bgr' or 'nv12', not {annotate_format!r}")
         self.pipe, self.gallery, self.thr = pipe, gallery, float(similarity_thresh)
         self.annotate, self.style = bool(annotate), style
         self.H, self.W = int(frame_hw[0]), int(frame_hw[1])
         self.nv12 = pixel_format == "nv12"
-        if self.nv12 and (self.H % 2 or self.W % 2):
+        self.out = "nv12" if annotate_format == "nv12" else None   # what pipe.draw is asked for
+        if (self.nv12 or self.out) and (self.H % 2 or self.W % 2):
             raise ValueError(f"NV12 frames have even sizes, not {self.W}x{self.H}")
         ctx = pipe.ctx
         shape = (pipe.B, self.H * 3 // 2, self.W) if self.nv12 else (pipe.B, self.H, self.W, 3)
@@ -60,6 +67,9 @@ class StreamRunner:
         # what a step hands to the pipeline: the staging buffer itself, or the NV12 view of it (dense layout)
         self.frames = [Nv12Frames(d, self.H, self.W, standard=standard) for d in self.dev] if self.nv12 else self.dev
         self.upload_bytes = self.host[0].nbytes
+        self.download_bytes = pipe.B * self.H * self.W * 3 // (2 if self.out else 1) if self.annotate else 0
+        if self.out and not self.nv12:
+            pipe.nv12_standard = standard
         self.tracked = isinstance(pipe, TrackedFacePipeline)
         self.stream = [np.zeros(pipe.B, np.int32) for _ in range(2)]      # camera of every frame of a staging buffer, -1 = padding
 
@@ -102,7 +112,10 @@ class StreamRunner:
             else:
                 self.pipe.run_step(self.frames[cur], self.H, self.W, self.gallery, self.thr)
             if self.annotate:                                       # the step's last reader of the clean frames has run
-                drawn_dev = self.pipe.draw(self.frames[cur], self.H, self.W, self.gallery, self.style)   # (NV12: the pipeline's BGR buffer)
+                # (BGR out of NV12 items: the pipeline's converted buffer; NV12 out of NV12 items: dev[cur] itself, drawn in place)
+                drawn_dev = self.pipe.draw(self.frames[cur], self.H, self.W, self.gallery, self.style, out=self.out)
+                if self.out:
+                    drawn_dev = drawn_dev.buf
             check(ctx.lib.fid_upload_release(ctx.handle, cur))     # dev[cur] is free again once this step has run
             nxt = cur ^ 1
             n_nxt = fill(nxt)                                       # host fills the other pinned buffer meanwhile
