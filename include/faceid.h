@@ -479,6 +479,71 @@ int fid_draw_faces_nv12_host(uint8_t *nv12, const fid_nv12_desc *desc, int B, in
                              const char *names, const int32_t *name_offsets, const uint8_t *bgr, int G, const fid_draw_style *style);
 int fid_draw_glyphs(uint8_t *out /* [95 * 7] */);
 
+/* ---- redacting faces on the frames: a mosaic or a solid fill over every selected face of a whole batch, in place on the device, enqueued
+ * behind the match with nothing read back first -- so that the video fid_draw_faces annotates may leave the box without showing passers-by.
+ * Nothing here is the reference's.  Integer arithmetic throughout; the device, the host twins and a numpy restatement agree to the byte.
+ *
+ * Faces.  The face count per frame and the three identity forms (idx == NULL; slots with id_stride; rows with offsets / n_rows) are
+ *   fid_draw_faces' own.  A face is KNOWN iff an idx array is given and its entry is >= 0 (no label table is involved); with idx == NULL every
+ *   face is unknown.  A face is SELECTED iff style.who has the bit of its class.  score is accepted and ignored (it keeps the argument shape).
+ * Box.  x1, y1, x2, y2 = the floats truncated toward zero; the face is skipped unless all four are finite, each |v| < 2^23, and
+ *   w = x2 - x1 > 0 && h = y2 - y1 > 0.
+ * Region, aligned on both axes to the 2 x 2 chroma grid so that BGR and NV12 share one geometry:
+ *   mx = (int)(expand * (double)w), my = (int)(expand * (double)h);
+ *   rx0 = x1 - mx rounded DOWN to even (floor, also for negatives), rx1 = (x2 + mx) | 1; ry0, ry1 likewise;
+ *   the region is the inclusive rectangle [rx0, rx1] x [ry0, ry1] intersected with the frame.
+ * Cells.  s = max(w, h); c = max(2, s / cells rounded UP to even) (integer division).  Cell (i, j) is
+ *   [rx0 + i*c, rx0 + (i+1)*c - 1] x [ry0 + j*c, ry0 + (j+1)*c - 1] intersected with the region and the frame: the grid is anchored at the
+ *   UNCLIPPED rx0, ry0, so it moves with the face and not with the frame edge.
+ * Values, MOSAIC.  BGR: per channel (sum + n / 2) / n over the n pixels of the clipped cell -- integer division, half rounds up; the sum is
+ *   exact for every frame the call accepts (it can pass 2^32).  NV12: Y the same mean over the cell's Y bytes, U and V each the same mean over
+ *   the cell's chroma pairs (H and W are even, region and cells even-aligned with an even size: every 2 x 2 group lies wholly inside or
+ *   outside a region, and inside one cell).  Nothing is converted: the BGR and the NV12 result are defined separately.
+ * Values, FILL.  BGR: fill_bgr.  NV12: Y(fill_bgr) and the (U, V) of the flat group 4 * fill_bgr with the layout's forward table, as
+ *   fid_draw_faces_nv12 colours a pixel.
+ * Several faces.  Every mean is taken from the frame AS IT WAS BEFORE THE CALL; a pixel (or an NV12 group) inside several selected regions
+ *   takes the value of the HIGHEST face index whose clipped region contains it (the overlay's order).  The result depends on no schedule.
+ *   Applying the call twice gives the first result again in every frame whose selected regions do not overlap, and under FILL always (a
+ *   cell of constant v has mean v); a cell partly under a higher face holds two values after the first call, and its mean moves.
+ * Written: only pixels inside a selected, clipped region.  NV12 padding (between W and pitch, between the planes, behind the last UV row,
+ *   between the frames) is never read or written.
+ *
+ * FID_E_INVALID, nothing enqueued, the frames untouched: everything fid_draw_faces refuses for the shared arguments (a NULL ctx, frames, det
+ * or counts; B, H, W or cap <= 0; B * cap or H * W * 3 not fitting int32; idx without score; id_stride <= 0 in the slot form; n_rows < 0); a
+ * NULL style, an unknown mode, who outside 1 .. 3, cells outside 1 .. 16, expand NaN or outside [0, 0.5], reserved != 0; for NV12 whatever
+ * fid_nv12_check refuses.  Asynchronous on the context's stream; never synchronises with the host, except once when the scratch is outgrown.
+ * The scratch holds, per face slot, a record, a 16-byte extent and a cell table of
+ *   (floor(1.5 * (1 + 2 * expand) * cells) + 3)^2 entries of 4 bytes (MOSAIC only)
+ * -- the most cells one face can have (derived in csrc/redact_core.h): 289 at the defaults, 2601 at cells = 16, expand = 0.5.
+ *
+ * Redaction destroys pixels: call it after the step's last reader of the clean frames (the warp, fid_face_measure, the best-shot crops), and
+ * before fid_draw_faces if boxes and names are to stay legible on top.  A mosaic is obfuscation, not cryptography; FILL is the strong mode.
+ * fid_redact_faces_host / fid_redact_faces_nv12_host: the same in plain loops on HOST arrays, no device involved: the table of cell values
+ * first, the writes second. */
+#define FID_REDACT_MOSAIC 0
+#define FID_REDACT_FILL 1
+#define FID_REDACT_UNKNOWN 1
+#define FID_REDACT_KNOWN 2
+typedef struct fid_redact_style {
+    int32_t mode;          /* FID_REDACT_MOSAIC 0 | FID_REDACT_FILL 1 */
+    int32_t who;           /* bit 0 FID_REDACT_UNKNOWN, bit 1 FID_REDACT_KNOWN; 0 is FID_E_INVALID */
+    int32_t cells;         /* mosaic cells along the LONGER side of the box, 1 .. 16 */
+    int32_t reserved;      /* 0 */
+    double  expand;        /* margin as a share of w and of h, [0, 0.5] */
+    uint8_t fill_bgr[4];   /* FILL colour (byte 3 unused) */
+} fid_redact_style;
+int fid_redact_faces(fid_ctx *ctx, uint8_t *frames_dev, int B, int H, int W, const float *det_dev, const int32_t *counts_dev, int cap,
+                     const int32_t *idx_dev, const float *score_dev, int id_stride, const int32_t *offsets_dev, int n_rows,
+                     const fid_redact_style *style);
+int fid_redact_faces_host(uint8_t *frames, int B, int H, int W, const float *det, const int32_t *counts, int cap, const int32_t *idx,
+                          const float *score, int id_stride, const int32_t *offsets, int n_rows, const fid_redact_style *style);
+int fid_redact_faces_nv12(fid_ctx *ctx, uint8_t *nv12_dev, const fid_nv12_desc *desc, int B, int H, int W, const float *det_dev,
+                          const int32_t *counts_dev, int cap, const int32_t *idx_dev, const float *score_dev, int id_stride,
+                          const int32_t *offsets_dev, int n_rows, const fid_redact_style *style);
+int fid_redact_faces_nv12_host(uint8_t *nv12, const fid_nv12_desc *desc, int B, int H, int W, const float *det, const int32_t *counts, int cap,
+                               const int32_t *idx, const float *score, int id_stride, const int32_t *offsets, int n_rows,
+                               const fid_redact_style *style);
+
 /* ---- face gates of the reference's product layer: replaces smart_face_recognition.py:1145-1216
  * (assess_face_quality), :1218-1297 (get_face_pose_angles / is_side_face), :1299-1399 (analyze_bbox_for_side_face) and the
  * best-face selection with its four rejections (:1473-1519), for every face of a batch in one launch on the post-process's own

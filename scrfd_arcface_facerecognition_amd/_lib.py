@@ -102,6 +102,23 @@ class DrawStyle(C.Structure):
         self.unknown_bgr[:3] = [int(v) for v in unknown_bgr]
 
 
+REDACT_MOSAIC, REDACT_FILL = 0, 1          # FID_REDACT_MOSAIC, FID_REDACT_FILL
+REDACT_UNKNOWN, REDACT_KNOWN = 1, 2        # FID_REDACT_UNKNOWN, FID_REDACT_KNOWN (bits of `who`)
+
+
+class RedactStyle(C.Structure):
+    """fid_redact_style (include/faceid.h): mosaic or solid fill, whom to redact (REDACT_UNKNOWN | REDACT_KNOWN), mosaic cells along the
+    longer side of the box (1 .. 16), margin as a share of the box's width and height ([0, 0.5]), FILL colour.  The default hides every face
+    that is not in the gallery behind an 8-cell mosaic."""
+    _fields_ = [("mode", C.c_int32), ("who", C.c_int32), ("cells", C.c_int32), ("reserved", C.c_int32), ("expand", C.c_double),
+                ("fill_bgr", C.c_uint8 * 4)]
+
+    def __init__(self, mode=REDACT_MOSAIC, who=REDACT_UNKNOWN, cells=8, expand=0.1, fill_bgr=(0, 0, 0)):
+        super().__init__()
+        self.mode, self.who, self.cells, self.reserved, self.expand = int(mode), int(who), int(cells), 0, float(expand)
+        self.fill_bgr[:3] = [int(v) for v in fill_bgr]
+
+
 MEASURE_KEYS = ("sharpness", "mean", "contrast", "clipped", "yaw", "pitch", "residual")       # words 0 .. 6 of a fid_face_measure row
 MEASURE_PIXELS_VALID, MEASURE_POSE_VALID = 1, 2                                                # stats word 7
 
@@ -181,6 +198,14 @@ SIGNATURES = {
     "fid_draw_faces_nv12_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                            C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "fid_draw_glyphs": (C.c_int, [C.c_void_p]),
+    "fid_redact_faces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "fid_redact_faces_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_int, C.c_void_p]),
+    "fid_redact_faces_nv12": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "fid_redact_faces_nv12_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "fid_abi_version": (C.c_int, []),
     "fid_last_error": (C.c_char_p, []),
     "fid_device_count": (C.c_int, [c_int_p]),

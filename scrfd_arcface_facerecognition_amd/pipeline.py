@@ -216,15 +216,30 @@ class FacePipeline:
             labels = labels.labels()
         return labels.handle
 
-    def _draw(self, frames_dev, H, W, labels, style, idx, score, id_stride, offsets=None, n_rows=0, track=None, out=None):
+    def _redact(self, frames_dev, H, W, style, idx, score, id_stride, offsets=None, n_rows=0):
+        """fid_redact_faces / fid_redact_faces_nv12 in place on frames_dev, with the identity arrays of the class's own draw"""
+        style = style if style is not None else _lib.RedactStyle()
+        if not isinstance(style, _lib.RedactStyle):
+            raise TypeError(f"redact: style must be a _lib.RedactStyle, not {type(style).__name__}")
+        name, lead = frame_reader("fid_redact_faces", frames_dev, H, W)
+        check(getattr(self.ctx.lib, name)(self.ctx.handle, *lead, self.B, int(H), int(W), C.c_void_p(self.post.det.ptr),
+                                          C.c_void_p(self.post.counts.ptr), self.post.cap, _lib._ptr(idx), _lib._ptr(score), int(id_stride),
+                                          _lib._ptr(offsets), int(n_rows), C.byref(style)))
+        return frames_dev
+
+    def _draw(self, frames_dev, H, W, labels, style, idx, score, id_stride, offsets=None, n_rows=0, track=None, out=None, redact=None):
         if out not in (None, "nv12"):
             raise ValueError(f"draw: out must be None or 'nv12', not {out!r}")
+        if redact is not None and not isinstance(redact, _lib.RedactStyle):
+            raise TypeError(f"draw: redact must be a _lib.RedactStyle or None, not {type(redact).__name__}")
         style = style if style is not None else _lib.DrawStyle()
         tail = (self.B, int(H), int(W), C.c_void_p(self.post.det.ptr), C.c_void_p(self.post.counts.ptr), self.post.cap, _lib._ptr(idx),
                 _lib._ptr(score), int(id_stride), _lib._ptr(offsets), int(n_rows), _lib._ptr(track), self._label_handle(labels), C.byref(style))
         if isinstance(frames_dev, _lib.Nv12Frames):
             _, lead = frame_reader("fid_nv12_to_bgr", frames_dev, H, W)
             if out == "nv12":                                  # in place on the two planes: no BGR frame anywhere
+                if redact is not None:
+                    self._redact(frames_dev, H, W, redact, idx, score, id_stride, offsets, n_rows)
                 check(self.ctx.lib.fid_draw_faces_nv12(self.ctx.handle, *lead, *tail))
                 return frames_dev
             # a BGR overlay needs BGR pixels: convert into the pipeline's own buffer, draw there
@@ -232,6 +247,8 @@ class FacePipeline:
                 self.bgr = self.ctx.empty((self.B, int(H), int(W), 3), np.uint8)
             check(self.ctx.lib.fid_nv12_to_bgr(self.ctx.handle, *lead, self.B, int(H), int(W), C.c_void_p(self.bgr.ptr)))
             frames_dev = self.bgr
+        if redact is not None:                                 # on the buffer about to be drawn on: boxes and names stay legible on top
+            self._redact(frames_dev, H, W, redact, idx, score, id_stride, offsets, n_rows)
         check(self.ctx.lib.fid_draw_faces(self.ctx.handle, _lib._ptr(frames_dev), *tail))
         if out == "nv12":                                      # BGR frames, drawn in place above: one conversion, half the bytes to download
             if self.nv12_out is None or (self.nv12_out.H, self.nv12_out.W) != (int(H), int(W)):
@@ -240,10 +257,24 @@ class FacePipeline:
             return self.nv12_out
         return frames_dev
 
-    def draw(self, frames_dev, H, W, labels, style=None, out=None):
+    def redact(self, frames_dev, H, W, style=None):
+        """Redact the last step's faces on frames_dev -- BGR uint8 [B,H,W,3], or the two planes of _lib.Nv12Frames --, in place and on the
+        device (fid_redact_faces / fid_redact_faces_nv12): a mosaic or a solid fill over every face `style` (_lib.RedactStyle; default: an
+        8-cell mosaic over the faces the match did not name) selects.  A face is known iff its entry of the identity array the class's own
+        `draw` uses is >= 0.  Enqueued behind the match; nothing is read back.  Redaction DESTROYS pixels: call it after the step's last
+        reader of the clean frames -- the warp (embed), measure and the best-shot crops, all inside run_step -- and before the buffer is
+        handed back to an upload.  Returns frames_dev."""
+        return self._redact(frames_dev, H, W, style, self.idx, self.score, self.F)
+
+    def draw(self, frames_dev, H, W, labels, style=None, out=None, redact=None):
         """Draw the last step's boxes, names and scores onto frames_dev uint8 [B,H,W,3], in place and on the device (fid_draw_faces): what
         frame_processor does with cv2 per face (main.py:132-148).  Enqueued behind the match; nothing is read back.  Call it after the
         step's last reader of the clean frames (run_step), and before the buffer is handed back to an upload.
+        redact: a _lib.RedactStyle: the selected faces are redacted (`redact`) on the buffer that is about to be drawn on, immediately
+        before the overlay, so that boxes and names stay legible on top of the mosaic -- on `self.bgr` for _lib.Nv12Frames with out=None
+        (the input stays untouched), in place on the planes with out="nv12", on the BGR frames before their conversion otherwise.  The same
+        ordering rule holds, the more so: redaction destroys pixels, so it runs after the step's last reader of the clean frames (the
+        warp, measure, the best-shot crops).
         labels: a LabelTable, a Gallery, or None; style: _lib.DrawStyle (default: the reference's look).
         out=None returns the BGR buffer that was drawn on: frames_dev itself, or -- for _lib.Nv12Frames, which are left untouched -- the
         pipeline's own BGR buffer `self.bgr` [B,H,W,3], filled by fid_nv12_to_bgr just before (overwritten by the next draw).
@@ -251,7 +282,7 @@ class FacePipeline:
         (fid_draw_faces_nv12; no BGR buffer is allocated) and returned; BGR frames are drawn in place as before and then converted once
         (fid_bgr_to_nv12, standard `self.nv12_standard`) into the pipeline's own dense buffer `self.nv12_out` (overwritten by the next
         draw; H and W even)."""
-        return self._draw(frames_dev, H, W, labels, style, self.idx, self.score, self.F, out=out)
+        return self._draw(frames_dev, H, W, labels, style, self.idx, self.score, self.F, out=out, redact=redact)
 
     # -- results -----------------------------------------------------------------------------------
     def results(self, gallery: Gallery):
@@ -343,7 +374,16 @@ class GroupedFacePipeline(FacePipeline):
         if steps:
             self.match(gallery, thresh, n=steps * self.n_slots)
 
-    def draw(self, frames_dev, H, W, labels, style=None, out=None):
+    def redact(self, frames_dev, H, W, style=None):
+        """FacePipeline.redact without identities: a step's identities exist only when its group's last step has run, so every face of the
+        step counts as unknown (the detections-only form).  A style that selects only known faces would silently redact nobody here and
+        is refused."""
+        style = style if style is not None else _lib.RedactStyle()
+        if isinstance(style, _lib.RedactStyle) and not (style.who & _lib.REDACT_UNKNOWN):
+            raise ValueError("GroupedFacePipeline.redact: no identities exist at the step; a style must select REDACT_UNKNOWN")
+        return self._redact(frames_dev, H, W, style, None, None, 0)
+
+    def draw(self, frames_dev, H, W, labels, style=None, out=None, redact=None):
         raise ValueError("GroupedFacePipeline.draw: a step's identities exist only when its group's last step has run, after its frames "
                          "may have been overwritten; draw from results() on the host (utils.helpers.draw_faces)")
 
@@ -514,10 +554,14 @@ class PackedFacePipeline(FacePipeline):
                 FacePipeline.match(self, gallery, thresh, n=n)
         self.ctx.sync()
 
-    def draw(self, frames_dev, H, W, labels, style=None, out=None):
+    def redact(self, frames_dev, H, W, style=None):
+        """FacePipeline.redact on the row table (the row form, as `draw`): a face without a row is not a face of the call"""
+        return self._redact(frames_dev, H, W, style, self.idx, self.score, 0, offsets=self.offsets, n_rows=min(self.n_run, self.row_cap))
+
+    def draw(self, frames_dev, H, W, labels, style=None, out=None, redact=None):
         """FacePipeline.draw on the row table: face f of frame b is row offsets[b] + f; only the rows the last step ran carry an identity"""
         return self._draw(frames_dev, H, W, labels, style, self.idx, self.score, 0, offsets=self.offsets, n_rows=min(self.n_run, self.row_cap),
-                          out=out)
+                          out=out, redact=redact)
 
     # -- results -----------------------------------------------------------------------------------
     def _download(self):
@@ -776,11 +820,19 @@ class TrackedFacePipeline(PackedFacePipeline):
         total = int(self.ctx.borrow(self.offsets.ptr + 4 * self.B, (1,), np.int32).download()[0])
         return min(total, self.row_cap)
 
-    def draw(self, frames_dev, H, W, labels, style=None, out=None):
+    def redact(self, frames_dev, H, W, style=None):
+        """FacePipeline.redact for EVERY detection, by its TRACK's identity (ident_idx, id_stride = cap): a person named earlier in the track
+        stays in the clear in the frames where the face was not embedded again"""
+        if not self._identified:
+            raise RuntimeError("TrackedFacePipeline: the last step has not been identified (match() / identify())")
+        return self._redact(frames_dev, H, W, style, self.ident_idx, self.ident_score, self.post.cap)
+
+    def draw(self, frames_dev, H, W, labels, style=None, out=None, redact=None):
         """FacePipeline.draw for EVERY detection, with its track's name and score; a style with the DRAW_TRACK_ID flag prints the track id"""
         if not self._identified:
             raise RuntimeError("TrackedFacePipeline: the last step has not been identified (match() / identify())")
-        return self._draw(frames_dev, H, W, labels, style, self.ident_idx, self.ident_score, self.post.cap, track=self.track, out=out)
+        return self._draw(frames_dev, H, W, labels, style, self.ident_idx, self.ident_score, self.post.cap, track=self.track, out=out,
+                          redact=redact)
 
     # -- results -----------------------------------------------------------------------------------
     def results_tracked(self, gallery: Optional[Gallery] = None):

@@ -205,6 +205,37 @@ def draw_faces(image, faces, colors=None, style=None):
                       track, style)
 
 
+def redact_faces(image, faces, known=None, style=None):
+    """Redact one frame's faces on `image` (uint8 [H,W,3], in place; returned) on the host (fid_redact_faces_host): a mosaic or a solid fill
+    over every face `style` (_lib.RedactStyle; default: an 8-cell mosaic over the unknown ones) selects.  faces: boxes (x1, y1, x2, y2, ...)
+    or entries of `results()` (bbox, det_score, kps, name, similarity, ...).  known: one truth value per face; None: an entry whose name is
+    not "Unknown" is known, a plain box is not.  Redact before draw_faces, so that boxes and names stay legible on top."""
+    from .._lib import RedactStyle, load
+    if getattr(image, "dtype", None) != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+        raise ValueError(f"redaction needs a uint8 [H,W,3] image, not {getattr(image, 'dtype', None)} {getattr(image, 'shape', None)}")
+    n = len(faces)
+    if n == 0:
+        return image
+    entries = [np.ndim(face[0]) > 0 for face in faces]
+    if known is None:
+        known = [e and face[3] != "Unknown" for e, face in zip(entries, faces)]
+    if len(known) != n:
+        raise ValueError(f"redact_faces: {len(known)} known flags for {n} faces")
+    buf = image if image.flags.c_contiguous and image.flags.writeable else np.ascontiguousarray(image)
+    H, W = buf.shape[:2]
+    det = np.zeros((n, 5), np.float32)
+    det[:, :4] = [np.asarray(face[0] if e else face, np.float32)[:4] for e, face in zip(entries, faces)]
+    counts = np.array([n], np.int32)
+    idx = np.array([0 if k else -1 for k in known], np.int32)
+    score = np.zeros(n, np.float32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    style = style if style is not None else RedactStyle()
+    check(load().fid_redact_faces_host(p(buf), 1, H, W, p(det), p(counts), n, p(idx), p(score), n, None, 0, C.byref(style)))
+    if buf is not image:
+        image[...] = buf
+    return image
+
+
 def draw_bbox(image, bbox, color=(0, 255, 0), thickness=3, proportion=0.2):
     cv2 = _cv2()
     if cv2 is None:

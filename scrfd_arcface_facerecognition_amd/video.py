@@ -45,14 +45,20 @@ class StreamRunner:
     the bytes to download.  NV12 items are drawn in place on the staging buffer's two planes (`pipe.draw(..., out="nv12")`: no BGR frame at
     all; the draw follows the step's last reader, and the download precedes the enqueue of that buffer's next upload, as on the BGR
     path); BGR items are drawn in place and converted once on the device, `standard` then being the output's standard.  H and W even.
+    redact (a _lib.RedactStyle, with annotate=True): `pipe.draw(..., redact=redact)`: the faces the style selects -- by default those the
+    match did not name -- are hidden behind a mosaic or a solid fill on the frame that is yielded, under the boxes and names, and nowhere
+    else: the step's readers (the warp, measure, the best-shot crops) have run on the clean frames before.
     `upload_bytes` is what one step uploads, `download_bytes` what one annotated step downloads (0 without annotate)."""
 
     def __init__(self, pipe: FacePipeline, gallery: Gallery, frame_hw, similarity_thresh: float = 0.4, annotate: bool = False, style=None,
-                 pixel_format: str = "bgr", standard: str = "bt601", annotate_format: str = "bgr"):
+                 pixel_format: str = "bgr", standard: str = "bt601", annotate_format: str = "bgr", redact=None):
         if pixel_format not in ("bgr", "nv12"):
             raise ValueError(f"pixel_format must be 'bgr' or 'nv12', not {pixel_format!r}")
         if annotate_format not in ("bgr", "nv12"):
             raise ValueError(f"annotate_format must be 'bgr' or 'nv12', not {annotate_format!r}")
+        if redact is not None and not annotate:
+            raise ValueError("redact needs annotate=True: the redacted frames are the annotated ones the runner yields")
+        self.redact = redact
         self.pipe, self.gallery, self.thr = pipe, gallery, float(similarity_thresh)
         self.annotate, self.style = bool(annotate), style
         self.H, self.W = int(frame_hw[0]), int(frame_hw[1])
@@ -113,7 +119,10 @@ class StreamRunner:
                 self.pipe.run_step(self.frames[cur], self.H, self.W, self.gallery, self.thr)
             if self.annotate:                                       # the step's last reader of the clean frames has run
                 # (BGR out of NV12 items: the pipeline's converted buffer; NV12 out of NV12 items: dev[cur] itself, drawn in place)
-                drawn_dev = self.pipe.draw(self.frames[cur], self.H, self.W, self.gallery, self.style, out=self.out)
+                if self.redact is not None:
+                    drawn_dev = self.pipe.draw(self.frames[cur], self.H, self.W, self.gallery, self.style, out=self.out, redact=self.redact)
+                else:
+                    drawn_dev = self.pipe.draw(self.frames[cur], self.H, self.W, self.gallery, self.style, out=self.out)
                 if self.out:
                     drawn_dev = drawn_dev.buf
             check(ctx.lib.fid_upload_release(ctx.handle, cur))     # dev[cur] is free again once this step has run
