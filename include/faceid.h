@@ -393,6 +393,78 @@ int fid_track_identify(fid_ctx *ctx, fid_tracker *trk, const int32_t *counts_dev
                        const int32_t *track_dev, const int32_t *offsets_dev, const int32_t *src_dev, int row_cap, const int32_t *idx_dev,
                        const float *score_dev, int n_rows, int32_t *ident_idx_dev, float *ident_score_dev);
 
+/* ---- coasting: a track's box in the frames where the detector missed it (no reference analogue: the reference draws what it detects,
+ * main.py:130-148, so a face the detector drops for three frames is shown in the clear for three frames).  A coaster follows a tracker on the
+ * device: for every frame of a step it emits the tracks that are alive but unmatched in that frame -- at their last box, optionally moved
+ * along their last velocity and grown per missed frame -- behind the frame's detections, in tables that fid_draw_faces* / fid_redact_faces*
+ * read unchanged in the slot form.  It changes nothing the tracker decides; fid_track_step never sees a prediction.
+ *
+ * State: S x T entries in device memory, owned by the handle, int32 x FID_COAST_WORDS each:
+ *   0 id (-1: free, then every other word is 0)   1 missed (frames since the last match)   2 has_vel   3 ident_idx   4 bits of ident_score
+ *   5 .. 8 bits of box x1 y1 x2 y2 (the last matched detection)   9 .. 12 bits of vel (per-frame deltas of x1 y1 x2 y2)   13 bits of conf
+ *   14, 15  0 (reserved).
+ * Config: hold in [0, 1023], the missed frames that are bridged; predict (0 / not 0); grow in [0, 0.5], not NaN; reserved 0.
+ *
+ * fid_track_coast follows one completed step, i.e. a step after its fid_track_identify (and after fid_track_keep, if any), with the step's
+ * stream, B, cap, det, counts, track and optionally fid_track_identify's ident_idx / ident_score [B,cap] (NULL together: every identity is
+ * (-1, 0)).  All fp32, every operation rounded on its own, the divide correctly rounded, no FMA.  Per stream, over its frames in batch order
+ * (stream[b] < 0 skips the frame), k_b = min(max(counts[b], 0), cap):
+ *   detections f = 0 .. k_b - 1.  A detection is TRACKED when its word track[b,f,1] >= 0, its id track[b,f,0] >= 0 and its slot s = word & 0xFF
+ *     is < T; any other detection touches no entry.  If a (malformed) track table names one slot twice in a frame, only the higher f is
+ *     applied.  The applied detection, against entry[s]:
+ *       continues   entry.id == id and the word has no FID_TRACK_STARTED:  d = (float)(missed + 1), vel_k = (det_k - box_k) / d for the four
+ *                   coordinates, has_vel = 1.  (After a gap the velocity is the mean over the gap.)
+ *       new         otherwise -- another id, or a track that STARTS under the same id, as after fid_tracker_reset --: id, vel = 0, has_vel = 0.
+ *       both        box = det[0..3], conf = det[4], missed = 0, (ident_idx, ident_score) = the detection's entries of the identity arrays.
+ *   end of frame: every entry with id >= 0 that took no detection in this frame gets missed = min(missed + 1, 1 << 20).  If
+ *     1 <= missed <= hold it COASTS in this frame:  m = (float)missed;  p_k = box_k + (vel_k * m) when predict && has_vel (the product is
+ *     rounded, then added), else p_k = box_k;  with grow != 0:  g = grow * m, dx = g * (p_x2 - p_x1), dy = g * (p_y2 - p_y1), the emitted box
+ *     is (p_x1 - dx, p_y1 - dy, p_x2 + dx, p_y2 + dy);  with grow == 0 the emitted box is p itself, so that without prediction it is the
+ *     last box bit for bit.  An entry past hold stays remembered (a later match resumes it, with the velocity over the long gap) but emits
+ *     nothing.  An entry ends only when another track takes its slot, or on fid_coaster_reset.
+ *   NaN: every float the call stores in the state or emits for a coasting entry -- box, vel, conf, ident_score -- is stored with a NaN
+ *     replaced by the quiet NaN 0x7FC00000 (fid_shot_score's rule: hosts and devices disagree on sign and payload).  The detections' own rows
+ *     are copied, not computed: they keep their bytes.
+ * Outputs (device), cap2 = cap + T: det_out float [B,cap2,5], counts_out int32 [B], track_out int32 [B,cap2,2], idx_out int32 [B,cap2],
+ * score_out float [B,cap2].  A frame of a live stream: first its k_b detections, copied verbatim from det, track, ident_idx and ident_score
+ * ((-1, 0) without identity arrays); then the entries that coast in this frame in ascending slot order: det row = (emitted box, conf), track =
+ * {id, slot | FID_TRACK_COASTED | (missed << 16)}, idx and score = the entry's identity, i.e. the track's as of its last matched frame;
+ * counts_out[b] = k_b + c_b; every row behind gets the fillers: det zeros, track {-1,-1}, idx -1, score 0.  A skipped frame has count 0 and
+ * only fillers.  Every byte of every output is defined.  The tables are fid_draw_faces* / fid_redact_faces*'s slot form with
+ * cap = id_stride = cap2: a named person coasts in the clear under the default redaction, a stranger behind the mosaic, and a coasted
+ * region, standing behind the detections, wins where it overlaps one (the highest-index rule).
+ * fid_coaster_reset: stream >= 0 frees that stream's entries, -1 all.  fid_coaster_read (synchronises; tests and debugging): entries_host
+ * int32 [S,T,FID_COAST_WORDS].
+ * FID_E_INVALID, nothing enqueued, outputs and state untouched: a NULL pointer (the two identity inputs may be NULL together, not one of
+ * them); S or T outside the tracker's ranges or different from the tracker's; B, cap or a stream array that differ from the tracker's last
+ * step's; B * cap2 not fitting int32; a tracker that has run no step, or whose step still waits for its identify; a second coast for the same
+ * step (the tracker counts its steps; skipping a step is allowed: the skipped frames do not age the entries); a bad config; a reset of a
+ * stream outside [-1, S).  fid_track_coast is asynchronous on the context's stream and never reads back; it synchronises only when B * T
+ * outgrows the context's scratch.
+ * fid_track_coast_host: the same walk in plain loops on HOST arrays, no device and no tracker involved (entries int32 [S,T,FID_COAST_WORDS] is
+ * the caller's, updated in place; a fresh state is id -1, every other word 0): the definition the kernels are tested against.  It refuses
+ * what can be checked without a tracker: NULL pointers, S < 1, T outside [1, 64], B or cap <= 0, B * cap2 overflow, a stream[b] >= S, a bad
+ * config. */
+typedef struct fid_coaster fid_coaster;
+typedef struct fid_coast_config {
+    int32_t hold;                  /* [0, 1023] */
+    int32_t predict;
+    float grow;                    /* [0, 0.5] */
+    int32_t reserved;              /* 0 */
+} fid_coast_config;
+#define FID_COAST_WORDS 16
+#define FID_TRACK_COASTED (1 << 10)
+int fid_coaster_create(fid_ctx *ctx, int S, int T, fid_coaster **out);
+int fid_coaster_destroy(fid_ctx *ctx, fid_coaster *coaster);
+int fid_coaster_reset(fid_ctx *ctx, fid_coaster *coaster, int stream);
+int fid_coaster_read(fid_ctx *ctx, fid_coaster *coaster, int32_t *entries_host);
+int fid_track_coast(fid_ctx *ctx, fid_coaster *coaster, fid_tracker *trk, const int32_t *stream, int B, int cap, const float *det_dev,
+                    const int32_t *counts_dev, const int32_t *track_dev, const int32_t *ident_idx_dev, const float *ident_score_dev,
+                    const fid_coast_config *cfg, float *det_out, int32_t *counts_out, int32_t *track_out, int32_t *idx_out, float *score_out);
+int fid_track_coast_host(int32_t *entries, int S, int T, const int32_t *stream, int B, int cap, const float *det, const int32_t *counts,
+                         const int32_t *track, const int32_t *ident_idx, const float *ident_score, const fid_coast_config *cfg,
+                         float *det_out, int32_t *counts_out, int32_t *track_out, int32_t *idx_out, float *score_out);
+
 /* ---- drawing detections, names and scores onto the frames (reference main.py:130-148 with utils/helpers.py:126-179 draw_bbox / draw_bbox_info):
  * the overlay of a whole batch in place on the device, enqueued behind the match with nothing read back first.  OpenCV's thick-line caps and
  * Hershey font are NOT reproduced; taken from the reference are the integer truncation of the box, the corner length, the

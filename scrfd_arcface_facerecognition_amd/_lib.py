@@ -83,6 +83,19 @@ class TrackConfig(C.Structure):
 
 TRACK_SLOT_WORDS = 10            # FID_TRACK_SLOT_WORDS
 TRACK_STARTED, TRACK_EMBED = 1 << 8, 1 << 9
+TRACK_COASTED = 1 << 10          # FID_TRACK_COASTED: a row the coaster appended; the word's bits 16 .. are the track's missed frames
+COAST_WORDS = 16                 # FID_COAST_WORDS: id, missed, has_vel, ident_idx, ident_score, box[4], vel[4], conf, 0 x 2
+
+
+class CoastConfig(C.Structure):
+    """fid_coast_config (include/faceid.h): missed frames a track's box is held for (0 .. 1023), whether the held box moves along the track's
+    last velocity, and the share of its width and height the box grows by on every side per missed frame ([0, 0.5]).
+    The defaults (5 frames, prediction on, 5 % per frame) are UNCALIBRATED: nobody has measured them on real video.  They are starting
+    points for a user's own calibration."""
+    _fields_ = [("hold", C.c_int32), ("predict", C.c_int32), ("grow", C.c_float), ("reserved", C.c_int32)]
+
+    def __init__(self, hold=5, predict=True, grow=0.05):
+        super().__init__(int(hold), int(bool(predict)), float(grow), 0)
 
 FID_LABEL_MAX = 32               # name bytes a label shows
 DRAW_TRACK_ID = 1                # FID_DRAW_TRACK_ID
@@ -287,6 +300,14 @@ SIGNATURES = {
                                  C.c_void_p, C.c_int]),
     "fid_track_identify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i32_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                      C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "fid_coaster_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_void_pp]),
+    "fid_coaster_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fid_coaster_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "fid_coaster_read": (C.c_int, [C.c_void_p, C.c_void_p, c_i32_p]),
+    "fid_track_coast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i32_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fid_track_coast_host": (C.c_int, [c_i32_p, C.c_int, C.c_int, c_i32_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fid_face_gates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
     "fid_face_measure": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -216,30 +216,38 @@ class FacePipeline:
             labels = labels.labels()
         return labels.handle
 
-    def _redact(self, frames_dev, H, W, style, idx, score, id_stride, offsets=None, n_rows=0):
-        """fid_redact_faces / fid_redact_faces_nv12 in place on frames_dev, with the identity arrays of the class's own draw"""
+    def _redact(self, frames_dev, H, W, style, idx, score, id_stride, offsets=None, n_rows=0, det=None, counts=None, cap=None):
+        """fid_redact_faces / fid_redact_faces_nv12 in place on frames_dev, with the identity arrays of the class's own draw; det / counts /
+        cap: another detection table than the post-process's (a coaster's extended one)"""
+        det = self.post.det if det is None else det
+        counts = self.post.counts if counts is None else counts
+        cap = self.post.cap if cap is None else int(cap)
         style = style if style is not None else _lib.RedactStyle()
         if not isinstance(style, _lib.RedactStyle):
             raise TypeError(f"redact: style must be a _lib.RedactStyle, not {type(style).__name__}")
         name, lead = frame_reader("fid_redact_faces", frames_dev, H, W)
-        check(getattr(self.ctx.lib, name)(self.ctx.handle, *lead, self.B, int(H), int(W), C.c_void_p(self.post.det.ptr),
-                                          C.c_void_p(self.post.counts.ptr), self.post.cap, _lib._ptr(idx), _lib._ptr(score), int(id_stride),
-                                          _lib._ptr(offsets), int(n_rows), C.byref(style)))
+        check(getattr(self.ctx.lib, name)(self.ctx.handle, *lead, self.B, int(H), int(W), C.c_void_p(det.ptr), C.c_void_p(counts.ptr), cap,
+                                          _lib._ptr(idx), _lib._ptr(score), int(id_stride), _lib._ptr(offsets), int(n_rows), C.byref(style)))
         return frames_dev
 
-    def _draw(self, frames_dev, H, W, labels, style, idx, score, id_stride, offsets=None, n_rows=0, track=None, out=None, redact=None):
+    def _draw(self, frames_dev, H, W, labels, style, idx, score, id_stride, offsets=None, n_rows=0, track=None, out=None, redact=None,
+              det=None, counts=None, cap=None):
         if out not in (None, "nv12"):
             raise ValueError(f"draw: out must be None or 'nv12', not {out!r}")
         if redact is not None and not isinstance(redact, _lib.RedactStyle):
             raise TypeError(f"draw: redact must be a _lib.RedactStyle or None, not {type(redact).__name__}")
         style = style if style is not None else _lib.DrawStyle()
-        tail = (self.B, int(H), int(W), C.c_void_p(self.post.det.ptr), C.c_void_p(self.post.counts.ptr), self.post.cap, _lib._ptr(idx),
+        tables = dict(det=det, counts=counts, cap=cap)         # (None: the post-process's own)
+        det = self.post.det if det is None else det
+        counts = self.post.counts if counts is None else counts
+        cap = self.post.cap if cap is None else int(cap)
+        tail = (self.B, int(H), int(W), C.c_void_p(det.ptr), C.c_void_p(counts.ptr), cap, _lib._ptr(idx),
                 _lib._ptr(score), int(id_stride), _lib._ptr(offsets), int(n_rows), _lib._ptr(track), self._label_handle(labels), C.byref(style))
         if isinstance(frames_dev, _lib.Nv12Frames):
             _, lead = frame_reader("fid_nv12_to_bgr", frames_dev, H, W)
             if out == "nv12":                                  # in place on the two planes: no BGR frame anywhere
                 if redact is not None:
-                    self._redact(frames_dev, H, W, redact, idx, score, id_stride, offsets, n_rows)
+                    self._redact(frames_dev, H, W, redact, idx, score, id_stride, offsets, n_rows, **tables)
                 check(self.ctx.lib.fid_draw_faces_nv12(self.ctx.handle, *lead, *tail))
                 return frames_dev
             # a BGR overlay needs BGR pixels: convert into the pipeline's own buffer, draw there
@@ -248,7 +256,7 @@ class FacePipeline:
             check(self.ctx.lib.fid_nv12_to_bgr(self.ctx.handle, *lead, self.B, int(H), int(W), C.c_void_p(self.bgr.ptr)))
             frames_dev = self.bgr
         if redact is not None:                                 # on the buffer about to be drawn on: boxes and names stay legible on top
-            self._redact(frames_dev, H, W, redact, idx, score, id_stride, offsets, n_rows)
+            self._redact(frames_dev, H, W, redact, idx, score, id_stride, offsets, n_rows, **tables)
         check(self.ctx.lib.fid_draw_faces(self.ctx.handle, _lib._ptr(frames_dev), *tail))
         if out == "nv12":                                      # BGR frames, drawn in place above: one conversion, half the bytes to download
             if self.nv12_out is None or (self.nv12_out.H, self.nv12_out.W) != (int(H), int(W)):
@@ -653,11 +661,26 @@ class TrackedFacePipeline(PackedFacePipeline):
                 The tracker still decides WHEN a face is embedded.  `finished_cap`: finished records the device holds between two
                 finished() calls (further ones are dropped and counted); `measure_config`: _lib.MeasureConfig, the score's three
                 normalisations (UNCALIBRATED defaults).  reset() needs no extra call: the next step's keep finishes what the reset orphaned.
-                Off (the default), nothing of this is launched or allocated."""
+                Off (the default), nothing of this is launched or allocated.
+
+    coast       a _lib.CoastConfig: match() follows identify() (and the keeper) with fid_track_coast: every track that is alive but found no
+                detection in a frame is appended to that frame's detections for up to `hold` frames -- at its last box, moved along its
+                last velocity (`predict`) and grown by `grow` per missed frame -- with its track's name.  redact() and draw() then work on
+                the extended tables [B, cap + max_tracks]: a redaction does not flicker off in the frames where the detector missed the
+                face, a named person stays in the clear, and the overlay shows the held box with the track's name and id.  hold > max_age
+                is a ValueError: the tracker has freed the track by then.  results() / results_tracked() are unchanged -- a coasted box is
+                not a detection --; results_coasted() lists the coasted entries.  The config's defaults are UNCALIBRATED.  None (the
+                default): nothing of this is launched or allocated."""
 
     def __init__(self, ctx: Context, det: CompiledNet, rec: CompiledNet, *, batch: int, row_cap: int, streams: int = 1, max_tracks: int = 64,
                  iou: float = 0.3, max_age: int = 15, refresh: int = 16, retry: int = 1, best_shot: bool = False, finished_cap: int = 256,
-                 keep_crops: bool = True, measure_config=None, **kw):
+                 keep_crops: bool = True, measure_config=None, coast=None, **kw):
+        if coast is not None:
+            if not isinstance(coast, _lib.CoastConfig):
+                raise TypeError(f"TrackedFacePipeline: coast must be a _lib.CoastConfig or None, not {type(coast).__name__}")
+            if coast.hold > int(max_age):
+                raise ValueError(f"TrackedFacePipeline: coast.hold = {coast.hold} exceeds max_age = {int(max_age)}: the tracker frees a track "
+                                 "after max_age missed frames, there is nothing left to hold")
         self.best_shot = bool(best_shot)
         if self.best_shot:
             kw["measure"] = True
@@ -684,12 +707,24 @@ class TrackedFacePipeline(PackedFacePipeline):
                                            C.byref(h)))
             self.shots = h
             self.shot_score = ctx.empty((self.row_cap,), np.float32)
+        self.coast, self.coaster, self._coasted = coast, None, False
+        if coast is not None:
+            h = C.c_void_p()
+            check(ctx.lib.fid_coaster_create(ctx.handle, self.streams, self.max_tracks, C.byref(h)))
+            self.coaster = h
+            cap2 = self.cap2 = cap + self.max_tracks
+            self.coast_det = ctx.empty((self.B, cap2, 5), np.float32)
+            self.coast_counts = ctx.empty((self.B,), np.int32)
+            self.coast_track = ctx.empty((self.B, cap2, 2), np.int32)
+            self.coast_idx = ctx.empty((self.B, cap2), np.int32)
+            self.coast_score = ctx.empty((self.B, cap2), np.float32)
 
     def _pack(self):
         check(self.ctx.lib.fid_track_step(self.ctx.handle, self.tracker, C.c_void_p(self.post.det.ptr), C.c_void_p(self.post.counts.ptr),
                                           self._stream.ctypes.data_as(_lib.c_i32_p), self.B, self.post.cap, C.byref(self.cfg),
                                           C.c_void_p(self.track.ptr), C.c_void_p(self.offsets.ptr), C.c_void_p(self.src.ptr), self.row_cap))
         self._identified = False
+        self._coasted = False                                 # (the extended tables are the previous step's until match() has run)
 
     def identify(self, n_rows: Optional[int] = None, idx=None, score=None):
         """fold the match of the last embed()'s rows back into the tracks (n_rows = 0: a step without a gallery or without a face)"""
@@ -712,6 +747,17 @@ class TrackedFacePipeline(PackedFacePipeline):
         if self.best_shot:
             self._names = gallery.names if gallery is not None else None
             self._keep(q)
+        if self.coaster:
+            self._coast()
+
+    def _coast(self):
+        """the step's detections plus the tracks that coast, into the extended tables (fid_track_coast; nothing is read back)"""
+        check(self.ctx.lib.fid_track_coast(self.ctx.handle, self.coaster, self.tracker, self._stream.ctypes.data_as(_lib.c_i32_p), self.B,
+                                           self.post.cap, C.c_void_p(self.post.det.ptr), C.c_void_p(self.post.counts.ptr),
+                                           C.c_void_p(self.track.ptr), C.c_void_p(self.ident_idx.ptr), C.c_void_p(self.ident_score.ptr),
+                                           C.byref(self.coast), C.c_void_p(self.coast_det.ptr), C.c_void_p(self.coast_counts.ptr),
+                                           C.c_void_p(self.coast_track.ptr), C.c_void_p(self.coast_idx.ptr), C.c_void_p(self.coast_score.ptr)))
+        self._coasted = True
 
     def _keep(self, q=None):
         """score the rows the last embed() ran and let the keeper see the step (with no row at all the keep still runs: ended tracks finish)"""
@@ -805,6 +851,8 @@ class TrackedFacePipeline(PackedFacePipeline):
         check(self.ctx.lib.fid_tracker_reset(self.ctx.handle, self.tracker, int(stream)))
         if stream < 0:
             self._identified = True
+        if self.coaster:                                      # (a held box of a forgotten track would outlive it)
+            check(self.ctx.lib.fid_coaster_reset(self.ctx.handle, self.coaster, int(stream)))
 
     def tracker_state(self) -> Tuple[np.ndarray, np.ndarray]:
         """(slots int32 [streams, max_tracks, 10], per-stream int32 [streams, 2] = next id, lost) -- fid_tracker_read; synchronises"""
@@ -823,14 +871,18 @@ class TrackedFacePipeline(PackedFacePipeline):
     def redact(self, frames_dev, H, W, style=None):
         """FacePipeline.redact for EVERY detection, by its TRACK's identity (ident_idx, id_stride = cap): a person named earlier in the track
         stays in the clear in the frames where the face was not embedded again"""
-        if not self._identified:
-            raise RuntimeError("TrackedFacePipeline: the last step has not been identified (match() / identify())")
+        self._need_coasted()
+        if self.coaster:                                      # ... and for every coasted track, behind the frame's detections
+            return self._redact(frames_dev, H, W, style, self.coast_idx, self.coast_score, self.cap2, det=self.coast_det,
+                                counts=self.coast_counts, cap=self.cap2)
         return self._redact(frames_dev, H, W, style, self.ident_idx, self.ident_score, self.post.cap)
 
     def draw(self, frames_dev, H, W, labels, style=None, out=None, redact=None):
         """FacePipeline.draw for EVERY detection, with its track's name and score; a style with the DRAW_TRACK_ID flag prints the track id"""
-        if not self._identified:
-            raise RuntimeError("TrackedFacePipeline: the last step has not been identified (match() / identify())")
+        self._need_coasted()
+        if self.coaster:                                      # a held box is drawn after the detections: it wins where they overlap
+            return self._draw(frames_dev, H, W, labels, style, self.coast_idx, self.coast_score, self.cap2, track=self.coast_track, out=out,
+                              redact=redact, det=self.coast_det, counts=self.coast_counts, cap=self.cap2)
         return self._draw(frames_dev, H, W, labels, style, self.ident_idx, self.ident_score, self.post.cap, track=self.track, out=out,
                           redact=redact)
 
@@ -858,6 +910,42 @@ class TrackedFacePipeline(PackedFacePipeline):
             out.append(faces)
         return out
 
+    def _need_coaster(self):
+        if self.coaster is None:
+            raise RuntimeError("TrackedFacePipeline: built without coast=CoastConfig(...)")
+
+    def _need_coasted(self):
+        """redact / draw / results_coasted read the extended tables: they must be this step's"""
+        if not self._identified:
+            raise RuntimeError("TrackedFacePipeline: the last step has not been identified (match() / identify())")
+        if self.coaster and not self._coasted:
+            raise RuntimeError("TrackedFacePipeline: the last step has not been coasted (match() runs fid_track_coast; identify() alone does not)")
+
+    def coaster_state(self) -> np.ndarray:
+        """the coaster's entries, int32 [streams, max_tracks, 16] (include/faceid.h: the words) -- fid_coaster_read; synchronises"""
+        self._need_coaster()
+        entries = np.empty((self.streams, self.max_tracks, _lib.COAST_WORDS), np.int32)
+        check(self.ctx.lib.fid_coaster_read(self.ctx.handle, self.coaster, entries.ctypes.data_as(_lib.c_i32_p)))
+        return entries
+
+    def results_coasted(self, gallery: Optional[Gallery] = None):
+        """Host view of the last step's coasted tracks: per frame, in slot order, (bbox[4], det_score, name, similarity, track id, missed)
+        -- the held box, the detection score and the name of the track's last matched frame, and the frames it has been missing for."""
+        self._need_coaster()
+        self._need_coasted()
+        counts, det, track = self.coast_counts.download(), self.coast_det.download(), self.coast_track.download()
+        ii, sc = self.coast_idx.download(), self.coast_score.download()
+        out = []
+        for b in range(self.B):
+            rows = []
+            for f in range(min(max(int(counts[b]), 0), self.cap2)):
+                word, j = int(track[b, f, 1]), int(ii[b, f])
+                if word >= 0 and word & _lib.TRACK_COASTED:
+                    rows.append((det[b, f, :4].copy(), float(det[b, f, 4]), gallery.names[j] if j >= 0 and gallery is not None else "Unknown",
+                                 float(sc[b, f]), int(track[b, f, 0]), word >> 16))
+            out.append(rows)
+        return out
+
     def results(self, gallery: Optional[Gallery] = None):
         """the list FacePipeline.results gives -- (bbox[4], det_score, kps[5,2], name, similarity) -- for every detection, name and
         similarity taken from its track"""
@@ -882,6 +970,9 @@ class TrackedFacePipeline(PackedFacePipeline):
         return self.rec.read(self.rec.low.outputs[0], kept).reshape(kept, -1), offsets
 
     def close(self):
+        if self.coaster:
+            self.ctx.lib.fid_coaster_destroy(self.ctx.handle, self.coaster)
+            self.coaster = None
         if self.shots:
             self.ctx.lib.fid_shots_destroy(self.ctx.handle, self.shots)
             self.shots = None

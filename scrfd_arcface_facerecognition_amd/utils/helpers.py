@@ -141,6 +141,39 @@ def measure_crops(crops, kps=None, M=None):
             for i in range(n)]
 
 
+# ---- coasting tracks through missed frames (no reference analogue: the reference draws what it detects) ----
+def coast_tracks(entries, stream, det, counts, track, ident_idx=None, ident_score=None, config=None):
+    """fid_track_coast_host on numpy arrays, no device: entries int32 [S,T,COAST_WORDS] (updated in place; a fresh state is id -1, every
+    other word 0), the step's stream [B], det [B,cap,5], counts [B], track [B,cap,2] and optionally fid_track_identify's ident_idx /
+    ident_score [B,cap]; config: _lib.CoastConfig (default: its UNCALIBRATED defaults).
+    -> (det [B,cap+T,5], counts [B], track [B,cap+T,2], idx [B,cap+T], score [B,cap+T]): every frame's detections, then its coasted tracks."""
+    from .._lib import COAST_WORDS, CoastConfig, load
+    if not (isinstance(entries, np.ndarray) and entries.dtype == np.int32 and entries.ndim == 3 and entries.shape[2] == COAST_WORDS
+            and entries.flags.c_contiguous):
+        raise ValueError(f"coast_tracks needs contiguous int32 [S,T,{COAST_WORDS}] entries")
+    S, T = entries.shape[:2]
+    det = np.ascontiguousarray(det, dtype=np.float32)
+    if det.ndim != 3 or det.shape[2] != 5:
+        raise ValueError(f"coast_tracks needs det [B,cap,5], not {det.shape}")
+    B, cap = det.shape[:2]
+    stream = np.ascontiguousarray(stream, dtype=np.int32).reshape(B)
+    counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(B)
+    track = np.ascontiguousarray(track, dtype=np.int32).reshape(B, cap, 2)
+    if (ident_idx is None) != (ident_score is None):
+        raise ValueError("coast_tracks: ident_idx and ident_score come together or not at all")
+    ii = None if ident_idx is None else np.ascontiguousarray(ident_idx, dtype=np.int32).reshape(B, cap)
+    sc = None if ident_score is None else np.ascontiguousarray(ident_score, dtype=np.float32).reshape(B, cap)
+    cfg = config if config is not None else CoastConfig()
+    cap2 = cap + T
+    outs = (np.empty((B, cap2, 5), np.float32), np.empty(B, np.int32), np.empty((B, cap2, 2), np.int32), np.empty((B, cap2), np.int32),
+            np.empty((B, cap2), np.float32))
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    check(load().fid_track_coast_host(i32(entries), S, T, i32(stream), B, cap, p(det), p(counts), p(track), p(ii), p(sc), C.byref(cfg),
+                                      *[p(o) for o in outs]))
+    return outs
+
+
 # ---- drawing (reference utils/helpers.py:126-179): with OpenCV on the host, cv2's primitives; without it, the library's host rasteriser
 # (fid_draw_faces_host: the raster rules of include/faceid.h -- the same pixels fid_draw_faces writes on the device) ----
 def _cv2():
