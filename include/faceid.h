@@ -932,6 +932,41 @@ int fid_gallery_group(fid_ctx *ctx, fid_gallery *g, const void *query_f16_dev, i
 #define FID_DEDUP_MAX_ROWS (1 << 20)
 int fid_gallery_dedup(fid_ctx *ctx, fid_gallery *g, const int32_t *rows_dev, int n, float thresh, int apply,
                       int32_t *keeper_dev, float *score_dev, int32_t *summary_dev);
+/* Density clusters of stored faces: "which of these n faces are the same person" as ONE asynchronous call whose answer does not depend on the
+ * order of the rows (fid_gallery_group and fid_gallery_dedup replay the reference's greedy loops and do).  No reference analogue: its
+ * `clustering_results/` are written by the greedy visit loop.
+ * rows_dev: int32 [n], the gallery row of every position k = 0 .. n - 1, as in fid_gallery_dedup; NULL = positions are the gallery rows
+ * 0 .. G - 1 and n is ignored.  A position TAKES PART when its row is inside [0, G) and holds a non-zero element (the sign bit does not count).
+ * hit(j, k) = the rule of fid_gallery_range: the fp32 cosine of the two stored fp16 rows is >= thresh and > 0.  A NaN never hits; a position
+ * that takes no part never hits and is never hit.
+ *   degree[k] = 1 + the number of OTHER positions that take part and hit k; 0 for a position that takes no part.
+ *   core[k]   = degree[k] >= min_pts (DBSCAN's min_samples: the point itself counts).
+ *   cluster   = a connected component of the hit graph restricted to core positions; its label is the LOWEST core position in it
+ *               (canonical: independent of any processing order).
+ *   via[k]    = for a position that takes part, the core position c != k with hit(c, k) and the highest score, the lowest position among
+ *               equal scores; score[k] = that cosine.  via -1 and score 0 when there is no such core.
+ *   label[k]  = a core's: its cluster's label.  A non-core position with via >= 0 is a BORDER: the label of via[k].  This is a deterministic
+ *               rule of this library -- sklearn's DBSCAN gives a border point to whichever cluster reaches it first.  Everything else: -1; a
+ *               position that takes part and has label -1 is NOISE.
+ * min_pts = 1 makes every position that takes part a core: plain connected components, singletons as clusters of one.
+ * Outputs (device), by position: label_dev, degree_dev, via_dev int32 [n]; score_dev float [n]; summary_dev int32 [6] = {clusters, cores,
+ * borders, noise, took part, fault}.  fault != 0: a union-find loop reached its bound of n + 1 steps, which no correct run does -- the labels
+ * are not to be trusted (the Python layer raises).
+ * FID_E_INVALID, nothing enqueued, outputs untouched: a NULL context, gallery or output pointer, n <= 0 or n > FID_CLUSTER_MAX_ROWS,
+ * min_pts < 1, thresh NaN or <= 0, dim % 32 != 0, a gallery beyond what a buffer descriptor addresses (4 GiB, as fid_gallery_range).
+ * Asynchronous on the context's stream; no host synchronisation beyond the scratch-arena rule of fid_match (see fid_gallery_group).  The
+ * gallery is never written.  Scratch: 12 bytes per position and one bit per pair of 128-position tiles (4 MB at 2^20 positions): no n x n
+ * matrix, no pair list.  FID_CLUSTER_SKIP=0 in the environment (read per call; measurements) makes the second pass compute every tile pair
+ * again instead of only those the first pass found a hit in; the answer does not depend on it.
+ * fid_cluster_host: the same rule in plain loops on HOST arrays (csrc/cluster_core.h), no device involved: rows_f16 [G, dim] fp16 rows in
+ * place of the gallery (any dim >= 1), rows int32 [n] or NULL, outputs as above.  Its cosine is the fp32 sum in ascending column order; the
+ * device sums in the order of its tiles.  Where the sums are exact the two are equal to the bit; elsewhere a pair within summation-order
+ * rounding of the threshold may fall on either side. */
+#define FID_CLUSTER_MAX_ROWS (1 << 20)
+int fid_gallery_cluster(fid_ctx *ctx, fid_gallery *g, const int32_t *rows_dev, int n, float thresh, int min_pts, int32_t *label_dev,
+                        int32_t *degree_dev, int32_t *via_dev, float *score_dev, int32_t *summary_dev);
+int fid_cluster_host(const void *rows_f16, int G, int dim, const int32_t *rows, int n, float thresh, int min_pts, int32_t *label,
+                     int32_t *degree, int32_t *via, float *score, int32_t *summary);
 /* Gallery sharded over ranks by contiguous row blocks (the 1 M-entry variant of main.py:136-142):
  * fid_match_keys scans THIS rank's rows (global index of its row 0 = first_row) for all n queries and writes one
  * packed key per query, (order-preserving bits of the score << 32) | ~global_index; after the ranks' key arrays

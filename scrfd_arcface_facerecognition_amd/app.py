@@ -233,6 +233,22 @@ class FaceAnalysis:
         self.last_batch_best = bests
         return out
 
+    def cluster_faces(self, images, similarity_threshold: float = 0.45, min_samples: int = 2, max_num: int = 0):
+        """Which faces of these images are the same person: get_batch(images, max_num), every face's embedding into a temporary VectorGallery
+        under the id (image index, face index), then VectorGallery.cluster.  Host glue only.  -> engine.ClusterResult keyed by those pairs;
+        the answer does not depend on the order of the images beyond the names of the labels.  The default threshold is the reference's
+        `grouping_threshold`; it is UNCALIBRATED for clustering."""
+        from .engine import VectorGallery
+        faces = self.get_batch(images, max_num)
+        ids = [(b, i) for b, fs in enumerate(faces) for i in range(len(fs))]
+        store = VectorGallery(self.ctx, 512, capacity=max(128, len(ids)))
+        try:
+            if ids:
+                store.upsert(ids, np.stack([faces[b][i]["embedding"] for b, i in ids]))
+            return store.cluster(similarity_threshold, min_samples)
+        finally:
+            store._gal.close()
+
     def process_visits(self, images, store, **thresholds):
         """The reference's process_visit_data (smart_face_recognition.py:1721-2005) for a list of images (sizes may differ), one visit each, in
         order: best face and its gates per image (the batch form of best_face, :1473-1519, through get_batch), then `store.group_visits` on the

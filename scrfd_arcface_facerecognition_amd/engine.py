@@ -3,6 +3,7 @@ gallery.  Everything here only moves pointers and shapes; all arithmetic happens
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -534,6 +535,28 @@ class VectorGallery:
         keeper, score, _ = self._dedup_call(ids, threshold, apply=False)
         return {ids[k]: (ids[int(keeper[k])], float(score[k])) for k in np.nonzero(keeper >= 0)[0]}
 
+    # ---- density clusters (fid_gallery_cluster): which stored faces are the same person, independent of the order of the rows --------------------
+    def cluster(self, similarity_threshold: float = 0.45, min_samples: int = 2, ids=None) -> "ClusterResult":
+        """Density clusters of the stored embeddings `ids` (default: all): two embeddings hit when their cosine is >= the threshold (and > 0); an
+        embedding with at least `min_samples` embeddings within the threshold, itself counted, is a core; a cluster is a connected set of cores
+        plus the borders that hang on them (include/faceid.h, fid_gallery_cluster, has the rule).  Positions are the ids in ascending order, as
+        in find_and_merge_duplicates(via="device"), so a cluster's label is its lowest core id -- but, unlike that greedy walk, the partition
+        does not depend on the order.  One upload (the rows), one call, one download (label | degree | via | score | summary as ONE buffer).
+        The default threshold is the reference's `grouping_threshold` (config.json); it is UNCALIBRATED for clustering."""
+        order = sorted(self.row_of if ids is None else ids)
+        n = len(order)
+        if n == 0:
+            return cluster_result([], np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.float32), np.zeros(6, np.int32))
+        if n > CLUSTER_MAX_ROWS:
+            raise ValueError(f"cluster: {n} embeddings exceed the {CLUSTER_MAX_ROWS} of one fid_gallery_cluster call")
+        ctx = self.ctx
+        rows_dev = ctx.to_device(np.asarray([self.row_of[i] for i in order], dtype=np.int32))
+        out = ctx.empty((4 * n + 6,), np.int32)
+        check(ctx.lib.fid_gallery_cluster(ctx.handle, self._gal.handle, C.c_void_p(rows_dev.ptr), n, C.c_float(similarity_threshold), int(min_samples),
+                                          C.c_void_p(out.ptr), C.c_void_p(out.ptr + 4 * n), C.c_void_p(out.ptr + 8 * n),
+                                          C.c_void_p(out.ptr + 12 * n), C.c_void_p(out.ptr + 16 * n)))
+        got = out.download()
+        return cluster_result(order, got[:n], got[n:2 * n], got[2 * n:3 * n], got[3 * n:4 * n].view(np.float32), got[4 * n:])
 
     # ---- the visit loop (fid_gallery_group): a batch of visits grouped into persons in visit order, one call, one download ------------------------
     def _next_ids(self):
@@ -767,6 +790,60 @@ def merges_from_keepers(ids_sorted, keeper, score):
     dead = [int(k) for k in np.nonzero(keeper >= 0)[0]]
     dead.sort(key=lambda k: (int(keeper[k]), -float(score[k]), k))
     return [(ids_sorted[int(keeper[k])], ids_sorted[k], float(score[k])) for k in dead]
+
+
+CLUSTER_MAX_ROWS = 1 << 20                                                        # FID_CLUSTER_MAX_ROWS
+
+
+class ClusterResult:
+    """What fid_gallery_cluster / fid_cluster_host answer, keyed by the caller's ids (ids[k] is the id at position k):
+    labels   {id: the label id of its cluster, or None}          (a cluster's label is its lowest core id)
+    clusters [[ids]], ordered by label and by position inside each list
+    noise    [ids] that took part and belong to no cluster;  degree {id: embeddings within the threshold, itself counted; 0 = took no part}
+    via      {id: (core id, score)}: the core that reaches the id with the highest score (a border hangs on it)
+    counts   {"clusters", "cores", "borders", "noise", "took_part"}
+    and the raw per-position arrays label_pos / degree_pos / via_pos / score_pos / summary."""
+
+    def __init__(self, ids, label, degree, via, score, summary):
+        self.ids = list(ids)
+        self.label_pos, self.degree_pos, self.via_pos = (np.array(a, np.int32) for a in (label, degree, via))
+        self.score_pos, self.summary = np.array(score, np.float32), np.array(summary, np.int32)
+        self.counts = dict(zip(("clusters", "cores", "borders", "noise", "took_part"), (int(v) for v in self.summary[:5])))
+
+    # (each view is built on first use: a store of 100 000 rows is 100 000 dictionary entries per view, more than the call itself costs)
+    @functools.cached_property
+    def labels(self):
+        ids = self.ids
+        return dict(zip(ids, [ids[l] if l >= 0 else None for l in self.label_pos.tolist()]))
+
+    @functools.cached_property
+    def clusters(self):
+        ids, label = self.ids, self.label_pos.tolist()
+        members: Dict[int, list] = {}
+        for k in np.nonzero(self.label_pos >= 0)[0].tolist():
+            members.setdefault(label[k], []).append(ids[k])
+        return [members[l] for l in sorted(members)]
+
+    @functools.cached_property
+    def noise(self):
+        ids = self.ids
+        return [ids[k] for k in np.nonzero((self.label_pos < 0) & (self.degree_pos > 0))[0].tolist()]
+
+    @functools.cached_property
+    def degree(self):
+        return dict(zip(self.ids, self.degree_pos.tolist()))
+
+    @functools.cached_property
+    def via(self):
+        ids, via, score = self.ids, self.via_pos.tolist(), self.score_pos.tolist()
+        return {ids[k]: (ids[via[k]], score[k]) for k in np.nonzero(self.via_pos >= 0)[0].tolist()}
+
+
+def cluster_result(ids, label, degree, via, score, summary) -> ClusterResult:
+    """the five output arrays of a clustering call as a ClusterResult; summary[5] != 0 (a union-find loop hit its bound) raises"""
+    if len(summary) > 5 and int(summary[5]) != 0:
+        raise RuntimeError("fid_gallery_cluster: a union-find loop reached its bound; the labels are not to be trusted")
+    return ClusterResult(ids, label, degree, via, score, summary)
 
 
 def _gallery_ptr(gal: Gallery) -> int:

@@ -174,6 +174,29 @@ def coast_tracks(entries, stream, det, counts, track, ident_idx=None, ident_scor
     return outs
 
 
+# ---- density clusters of embeddings (no reference analogue: its clustering_results/ come from the greedy visit loop) ----
+def cluster_embeddings(embeddings, threshold: float = 0.45, min_samples: int = 2):
+    """fid_cluster_host on numpy arrays, no device: embeddings [n, dim] (any scale; a zero row takes no part) are normalised in float64 and
+    rounded to fp16 as the gallery stores them, then clustered by the rule of fid_gallery_cluster (include/faceid.h): two rows hit at a cosine
+    >= threshold (and > 0), a row with `min_samples` rows within the threshold, itself counted, is a core, clusters are connected cores plus
+    their borders, labelled by their lowest core.  The answer does not depend on the order of the rows.  The default threshold is the
+    reference's `grouping_threshold`; it is UNCALIBRATED for clustering.  -> engine.ClusterResult keyed by the row index."""
+    from .._lib import load
+    from ..engine import cluster_result
+    x = np.asarray(embeddings, dtype=np.float64)
+    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"cluster_embeddings needs embeddings [n, dim], not {x.shape}")
+    n, dim = x.shape
+    nrm = np.sqrt((x * x).sum(1, keepdims=True))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        unit = np.ascontiguousarray(np.where(nrm > 0, x / np.where(nrm > 0, nrm, 1), 0).astype(np.float16))
+    label, degree, via = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32)
+    score, summary = np.empty(n, np.float32), np.empty(6, np.int32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    check(load().fid_cluster_host(p(unit), n, dim, None, n, C.c_float(threshold), int(min_samples), p(label), p(degree), p(via), p(score), p(summary)))
+    return cluster_result(list(range(n)), label, degree, via, score, summary)
+
+
 # ---- drawing (reference utils/helpers.py:126-179): with OpenCV on the host, cv2's primitives; without it, the library's host rasteriser
 # (fid_draw_faces_host: the raster rules of include/faceid.h -- the same pixels fid_draw_faces writes on the device) ----
 def _cv2():
