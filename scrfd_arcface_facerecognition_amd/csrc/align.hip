@@ -35,15 +35,38 @@ struct Nv12Src {
     fid_yuv_coeffs k;
     __device__ __forceinline__ void load(int y, int x, int (&v)[3]) const { fid_nv12_pixel(k, yp, uvp, pitch, y0 + y, x0 + x, v); }
 };
-// a batch of NV12 frames as a kernel argument (fid_nv12_desc with the standard's integers resolved on the host)
-struct Nv12Batch {
+
+// A batch of frames as a by-value kernel argument: frame(b) gives image b's source and its size, frame(b, x0, y0) the part of it whose
+// top-left pixel is (x0, y0).  The kernels below are written once over these.
+template <class Src>
+struct Frame {
+    Src src;
+    int H, W;
+};
+struct BgrBatch {            // dense uint8 [B, H, W, 3]
+    const uint8_t *p;
+    int H, W;
+    __device__ __forceinline__ Frame<BgrSrc> frame(int b, int x0 = 0, int y0 = 0) const {
+        return {BgrSrc{p + (((size_t)b * H + y0) * W + x0) * 3, W}, H, W};
+    }
+};
+struct RaggedBatch {         // mixed sizes: image b's base, H and W from the per-image table (block-uniform index: the entry stays in scalar registers)
+    const uint8_t *p;
+    const fid::RaggedImg *tab;   // (the host's entries until upload_table has run)
+    __device__ __forceinline__ Frame<BgrSrc> frame(int b) const {
+        const fid::RaggedImg g = tab[b];
+        return {BgrSrc{p + g.off, g.W}, g.H, g.W};
+    }
+};
+struct Nv12Batch {           // fid_nv12_desc with the standard's integers resolved on the host
     const uint8_t *p;
     long long frame_stride, uv_offset;
     int pitch;
     fid_yuv_coeffs k;
-    __device__ __forceinline__ Nv12Src frame(int b, int x0 = 0, int y0 = 0) const {
+    int H, W;
+    __device__ __forceinline__ Frame<Nv12Src> frame(int b, int x0 = 0, int y0 = 0) const {
         const uint8_t *f = p + (size_t)b * (size_t)frame_stride;
-        return Nv12Src{f, f + uv_offset, pitch, x0, y0, k};
+        return {Nv12Src{f, f + uv_offset, pitch, x0, y0, k}, H, W};
     }
 };
 
@@ -61,8 +84,7 @@ constexpr int ROWS_PER_BLOCK = 16;
 
 // One block's share (ROWS_PER_BLOCK output rows from y0) of one face's crop: thread 0 estimates the transform from the landmarks `lm`
 // (NULL = no face: zero crop, zero M), every thread warps.  `src` = the face's frame, `dst` = its crop, `mo` = its row of M_out (or NULL).
-// Shared by align_warp (face slots) and align_warp_packed (dense row table): the two produce the same bytes by construction; so do their
-// NV12 forms, whose taps are converted by the source before they are weighted.
+// An NV12 source converts its taps before they are weighted.
 template <class Src>
 __device__ __forceinline__ void align_face_rows(const Src &src, int H, int W, const float *lm, uint8_t *dst, double *mo, int y0) {
     const bool valid = lm != nullptr;
@@ -129,70 +151,61 @@ __device__ __forceinline__ void align_face_rows(const Src &src, int H, int W, co
     }
 }
 
-__global__ void __launch_bounds__(256) align_warp(const uint8_t *frames, int H, int W, const float *kps, const int *counts,
-                                                  int cap, int F, uint8_t *crops, double *M_out) {
-    const int slot = blockIdx.y;  // b * F + f
-    const int b = slot / F, f = slot - b * F;
-    const bool valid = f < counts[b] && f < cap;
-    align_face_rows(BgrSrc{frames + (size_t)b * H * W * 3, W}, H, W, valid ? kps + ((size_t)b * cap + f) * 10 : nullptr,
-                    crops + (size_t)slot * OUT * OUT * 3, M_out ? M_out + (size_t)slot * 6 : nullptr, blockIdx.x * ROWS_PER_BLOCK);
+// Which face output row blockIdx.y holds: its frame, its row of the post-process's landmark array (face b * cap + f), and whether there is one.
+struct FaceRow {
+    int b;
+    size_t lm;
+    bool valid;
+};
+struct SlotRows {            // B x F face slots: row b * F + f is face f of frame b, empty from counts[b] on
+    const int *counts;
+    int cap, F;
+    __device__ __forceinline__ FaceRow at(int slot) const {
+        const int b = slot / F, f = slot - b * F;
+        return {b, (size_t)b * cap + f, f < counts[b] && f < cap};
+    }
+};
+// a dense row table (fid_face_pack): row i holds face src_rows[i] = b * cap + f, or -1 = no face (reference main.py:130-134 embeds every
+// face models/scrfd.py:159-177 returned; the table lists them without per-frame padding)
+struct PackedRows {
+    const int *src_rows;
+    int B, cap;
+    __device__ __forceinline__ FaceRow at(int row) const {
+        const int s = src_rows[row];
+        const bool valid = s >= 0 && s < B * cap;
+        return {valid ? s / cap : 0, (size_t)s, valid};
+    }
+};
+
+template <class Frames, class Rows>
+__global__ void __launch_bounds__(256) align_warp(Frames frames, Rows rows, const float *kps, uint8_t *crops, double *M_out) {
+    const FaceRow r = rows.at(blockIdx.y);
+    const auto f = frames.frame(r.b);
+    align_face_rows(f.src, f.H, f.W, r.valid ? kps + r.lm * 10 : nullptr, crops + (size_t)blockIdx.y * OUT * OUT * 3,
+                    M_out ? M_out + (size_t)blockIdx.y * 6 : nullptr, blockIdx.x * ROWS_PER_BLOCK);
 }
 
-__global__ void __launch_bounds__(256) align_warp_nv12(Nv12Batch nv, int H, int W, const float *kps, const int *counts,
-                                                       int cap, int F, uint8_t *crops, double *M_out) {
-    const int slot = blockIdx.y;  // b * F + f
-    const int b = slot / F, f = slot - b * F;
-    const bool valid = f < counts[b] && f < cap;
-    align_face_rows(nv.frame(b), H, W, valid ? kps + ((size_t)b * cap + f) * 10 : nullptr,
-                    crops + (size_t)slot * OUT * OUT * 3, M_out ? M_out + (size_t)slot * 6 : nullptr, blockIdx.x * ROWS_PER_BLOCK);
+// cv2.resize's INTER_LINEAR rule for output coordinate d of an axis with n source pixels: the two taps s0, s1 and their 11-bit weights a0, a1
+__device__ __forceinline__ void resize_coeff(int d, double scale, int n, int &s0, int &s1, int &a0, int &a1) {
+    float f = (float)(((double)d + 0.5) * scale - 0.5);
+    int s = (int)floorf(f);
+    f -= (float)s;
+    if (s < 0) { s = 0; f = 0.f; }
+    if (s >= n - 1) { s = n - 1; f = 0.f; }
+    s0 = s; s1 = min(s + 1, n - 1);
+    a1 = (int)rintf(__fmul_rn(f, 2048.f));
+    a0 = (int)rintf(__fmul_rn(__fsub_rn(1.f, f), 2048.f));
 }
 
-// The same for a dense row table (fid_face_pack): row i holds face src[i] = b * cap + f of the post-process's arrays, or -1 = no face
-// (reference main.py:130-134 embeds every face models/scrfd.py:159-177 returned; the table lists them without per-frame padding).
-__global__ void __launch_bounds__(256) align_warp_packed(const uint8_t *frames, int B, int H, int W, const float *kps, int cap,
-                                                         const int *src_rows, uint8_t *crops, double *M_out) {
-    const int row = blockIdx.y;
-    const int s = src_rows[row];
-    const bool valid = s >= 0 && s < B * cap;
-    const int b = valid ? s / cap : 0;
-    align_face_rows(BgrSrc{frames + (size_t)b * H * W * 3, W}, H, W, valid ? kps + (size_t)s * 10 : nullptr,
-                    crops + (size_t)row * OUT * OUT * 3, M_out ? M_out + (size_t)row * 6 : nullptr, blockIdx.x * ROWS_PER_BLOCK);
-}
-
-__global__ void __launch_bounds__(256) align_warp_packed_nv12(Nv12Batch nv, int B, int H, int W, const float *kps, int cap,
-                                                              const int *src_rows, uint8_t *crops, double *M_out) {
-    const int row = blockIdx.y;
-    const int s = src_rows[row];
-    const bool valid = s >= 0 && s < B * cap;
-    align_face_rows(nv.frame(valid ? s / cap : 0), H, W, valid ? kps + (size_t)s * 10 : nullptr,
-                    crops + (size_t)row * OUT * OUT * 3, M_out ? M_out + (size_t)row * 6 : nullptr, blockIdx.x * ROWS_PER_BLOCK);
-}
-
-// Mixed-size batches (fid_align_crops_ragged / fid_align_crops_packed_ragged): the same two kernels with frame b's base pointer and
-// H, W read from the per-image table (fid::RaggedImg; block-uniform index, so the entry stays in scalar registers).
-__global__ void __launch_bounds__(256) align_warp_ragged(const uint8_t *frames, const fid::RaggedImg *tab, const float *kps, const int *counts,
-                                                         int cap, int F, uint8_t *crops, double *M_out) {
-    const int slot = blockIdx.y;  // b * F + f
-    const int b = slot / F, f = slot - b * F;
-    const bool valid = f < counts[b] && f < cap;
-    const fid::RaggedImg g = tab[b];
-    align_face_rows(BgrSrc{frames + g.off, g.W}, g.H, g.W, valid ? kps + ((size_t)b * cap + f) * 10 : nullptr,
-                    crops + (size_t)slot * OUT * OUT * 3, M_out ? M_out + (size_t)slot * 6 : nullptr, blockIdx.x * ROWS_PER_BLOCK);
-}
-
-__global__ void __launch_bounds__(256) align_warp_packed_ragged(const uint8_t *frames, const fid::RaggedImg *tab, int B, const float *kps, int cap,
-                                                                const int *src_rows, uint8_t *crops, double *M_out) {
-    const int row = blockIdx.y;
-    const int s = src_rows[row];
-    const bool valid = s >= 0 && s < B * cap;
-    const fid::RaggedImg g = tab[valid ? s / cap : 0];
-    align_face_rows(BgrSrc{frames + g.off, g.W}, g.H, g.W, valid ? kps + (size_t)s * 10 : nullptr,
-                    crops + (size_t)row * OUT * OUT * 3, M_out ? M_out + (size_t)row * 6 : nullptr, blockIdx.x * ROWS_PER_BLOCK);
+// the 12 bytes of four BGR pixels as three dwords
+__device__ __forceinline__ void store_quad(const uint8_t (&px)[12], unsigned *o) {
+#pragma unroll
+    for (int j = 0; j < 3; j++)
+        o[j] = (unsigned)px[4 * j] | ((unsigned)px[4 * j + 1] << 8) | ((unsigned)px[4 * j + 2] << 16) | ((unsigned)px[4 * j + 3] << 24);
 }
 
 // cv2.resize INTER_LINEAR u8 + zero letterbox paste (scrfd.py:135-138): output pixel (x, y) of one image, written to o.
-// Shared by the uniform, the mixed-size and the tile kernels and their NV12 forms: they write the same bytes by construction.  `src` is the
-// H x W image (a dense image, or a rectangle of a frame for fid_tile_cut); an NV12 source converts each of the pixels asked for below.
+// `src` is the H x W image (a dense image, or a rectangle of a frame for fid_tile_cut); an NV12 source converts each of the pixels asked for below.
 template <class Src>
 __device__ __forceinline__ void letterbox_pixel(const Src &src, int H, int W, uint8_t *o, int x, int y, int new_h, int new_w,
                                                 double scale_x, double scale_y, int area2x) {
@@ -209,19 +222,9 @@ __device__ __forceinline__ void letterbox_pixel(const Src &src, int H, int W, ui
         for (int c = 0; c < 3; c++) o[c] = (uint8_t)((p00[c] + p01[c] + p10[c] + p11[c] + 2) >> 2);
         return;
     }
-    auto coeff = [](int d, double scale, int n, int &s0, int &s1, int &a0, int &a1) {
-        float f = (float)(((double)d + 0.5) * scale - 0.5);
-        int s = (int)floorf(f);
-        f -= (float)s;
-        if (s < 0) { s = 0; f = 0.f; }
-        if (s >= n - 1) { s = n - 1; f = 0.f; }
-        s0 = s; s1 = min(s + 1, n - 1);
-        a1 = (int)rintf(__fmul_rn(f, 2048.f));
-        a0 = (int)rintf(__fmul_rn(__fsub_rn(1.f, f), 2048.f));
-    };
     int sx0, sx1, a0, a1, sy0, sy1, b0, b1;
-    coeff(x, scale_x, W, sx0, sx1, a0, a1);
-    coeff(y, scale_y, H, sy0, sy1, b0, b1);
+    resize_coeff(x, scale_x, W, sx0, sx1, a0, a1);
+    resize_coeff(y, scale_y, H, sy0, sy1, b0, b1);
     src.load(sy0, sx0, p00); src.load(sy0, sx1, p01);
     src.load(sy1, sx0, p10); src.load(sy1, sx1, p11);
     for (int c = 0; c < 3; c++) {
@@ -241,34 +244,52 @@ __device__ __forceinline__ void letterbox_quad(const Src &src, int H, int W, uns
     uint8_t px[12];
 #pragma unroll
     for (int i = 0; i < 4; i++) letterbox_pixel(src, H, W, px + 3 * i, x4 + i, y, new_h, new_w, scale_x, scale_y, area2x);
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-        o[j] = (unsigned)px[4 * j] | ((unsigned)px[4 * j + 1] << 8) | ((unsigned)px[4 * j + 2] << 16) | ((unsigned)px[4 * j + 3] << 24);
+    store_quad(px, o);
 }
 
-__global__ void __launch_bounds__(256) letterbox_kernel(const uint8_t *frames, int H, int W, uint8_t *out, int in_h, int in_w,
-                                                        int new_h, int new_w, double scale_x, double scale_y, int area2x) {
-    const int b = blockIdx.z;
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= in_w) return;
-    letterbox_pixel(BgrSrc{frames + (size_t)b * H * W * 3, W}, H, W, out + (((size_t)b * in_h + y) * in_w + x) * 3, x, y, new_h, new_w, scale_x,
-                    scale_y, area2x);
-}
+// Where the one-pixel kernel's image blockIdx.z and its letterbox geometry come from: pixel(frames, z, o, x, y) writes output pixel (x, y).
+struct UniformGeom {         // every image of the batch alike: the geometry travels as kernel arguments
+    int new_h, new_w;
+    double scale_x, scale_y;
+    int area2x;
+    template <class Frames>
+    __device__ __forceinline__ void pixel(const Frames &frames, int b, uint8_t *o, int x, int y) const {
+        const auto f = frames.frame(b);
+        letterbox_pixel(f.src, f.H, f.W, o, x, y, new_h, new_w, scale_x, scale_y, area2x);
+    }
+};
+struct RaggedGeom {          // a mixed-size batch: the image's entry of the batch's table; identity and exact-2x are decided per image
+    __device__ __forceinline__ void pixel(const RaggedBatch &frames, int b, uint8_t *o, int x, int y) const {
+        const fid::RaggedImg g = frames.tab[b];
+        letterbox_pixel(BgrSrc{frames.p + g.off, g.W}, g.H, g.W, o, x, y, g.new_h, g.new_w, g.scale_x, g.scale_y, g.mode == 2);
+    }
+};
+// Tile t of the table (fid_tile_cut), cut from its frame.  The rectangle's pixels are addressed in FRAME coordinates, so an odd (x0, y0)
+// keeps an NV12 frame's chroma grid.  (kind 0: new_h x new_w == h x w, which letterbox_pixel copies 1:1 and pads with zeros)
+struct TileGeom {
+    const fid::TileEntry *tab;
+    template <class Frames>
+    __device__ __forceinline__ void pixel(const Frames &frames, int t, uint8_t *o, int x, int y) const {
+        const fid::TileEntry g = tab[t];
+        letterbox_pixel(frames.frame(g.frame, g.x0, g.y0).src, g.h, g.w, o, x, y, g.new_h, g.new_w, g.scale_x, g.scale_y, g.mode == 2);
+    }
+};
 
-__global__ void __launch_bounds__(256) letterbox_kernel_nv12(Nv12Batch nv, int H, int W, uint8_t *out, int in_h, int in_w,
-                                                             int new_h, int new_w, double scale_x, double scale_y, int area2x) {
-    const int b = blockIdx.z;
+// one output pixel per thread: image (or tile) blockIdx.z into its own in_h x in_w detector input
+template <class Frames, class Geom>
+__global__ void __launch_bounds__(256) letterbox_kernel(Frames frames, Geom geom, uint8_t *out, int in_h, int in_w) {
+    const int z = blockIdx.z;
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= in_w) return;
-    letterbox_pixel(nv.frame(b), H, W, out + (((size_t)b * in_h + y) * in_w + x) * 3, x, y, new_h, new_w, scale_x, scale_y, area2x);
+    geom.pixel(frames, z, out + (((size_t)z * in_h + y) * in_w + x) * 3, x, y);
 }
 
 // fid_nv12_to_bgr: two horizontally adjacent pixels per thread (they share one chroma sample), dense BGR out
-__global__ void __launch_bounds__(256) nv12_to_bgr_kernel(Nv12Batch nv, int H, int W, uint8_t *out) {
-    const int b = blockIdx.z;
+__global__ void __launch_bounds__(256) nv12_to_bgr_kernel(Nv12Batch nv, uint8_t *out) {
+    const int b = blockIdx.z, H = nv.H, W = nv.W;
     const int x = (blockIdx.x * blockDim.x + threadIdx.x) * 2, y = blockIdx.y;
     if (x >= W) return;
-    const Nv12Src s = nv.frame(b);
+    const Nv12Src s = nv.frame(b).src;
     const uint8_t *yr = s.yp + (size_t)y * s.pitch + x, *c = s.uvp + (size_t)(y >> 1) * s.pitch + x;      // (x is even: the pair's own sample)
     int v0[3], v1[3];
     fid_yuv_to_bgr(s.k, yr[0], c[0], c[1], v0);
@@ -346,24 +367,13 @@ __global__ void __launch_bounds__(256) bgr_to_nv12_kernel(const uint8_t *__restr
     }
 }
 
-// a mixed-size batch: image blockIdx.z's geometry comes from the table; identity and exact-2x are decided per image
-__global__ void __launch_bounds__(256) letterbox_kernel_ragged(const uint8_t *frames, const fid::RaggedImg *tab, uint8_t *out, int in_h, int in_w) {
-    const int b = blockIdx.z;
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= in_w) return;
-    const fid::RaggedImg g = tab[b];
-    letterbox_pixel(BgrSrc{frames + g.off, g.W}, g.H, g.W, out + (((size_t)b * in_h + y) * in_w + x) * 3, x, y, g.new_h, g.new_w, g.scale_x, g.scale_y,
-                    g.mode == 2);
-}
-
-// The same arithmetic, FOUR consecutive output pixels per thread (in_w % 4 == 0): a source pixel is one unaligned 4-byte load instead of three
-// 1-byte loads and the 12 output bytes leave as three aligned dwords -- 16 + 3 memory instructions per 4 pixels instead of 48 + 12 (32 frames of
-// 1080p -> 640x640: cfg 5 step 1.548 -> 1.535 ms).  `src_bytes` = bytes of the whole frame batch: the last pixel of the batch is read bytewise.
-// Shared by the uniform and the mixed-size kernel, like letterbox_pixel.
+// letterbox_pixel's bilinear arithmetic, FOUR consecutive output pixels per thread (in_w % 4 == 0): a source pixel is one unaligned 4-byte load
+// instead of three 1-byte loads and the 12 output bytes leave as three aligned dwords -- 16 + 3 memory instructions per 4 pixels instead of 48 + 12
+// (32 frames of 1080p -> 640x640: cfg 5 step 1.548 -> 1.535 ms).  `src_bytes` = bytes of the whole frame batch: the last pixel of the batch is read bytewise.
 // letterbox_pixels4: output pixels x4 .. x4+3 of row y of the image whose first byte is frames[fbase] (rows `ld` pixels apart), as three dwords at o.
 __device__ __forceinline__ void letterbox_pixels4(const uint8_t *frames, size_t fbase, int H, int W, int ld, unsigned *o, int x4, int y, int new_h, int new_w,
                                                   double scale_x, double scale_y, size_t src_bytes) {
-    unsigned char px[12];
+    uint8_t px[12];
     auto fetch = [&](size_t off) -> unsigned {                  // the 3 bytes of a source pixel (byte 3 of the word is ignored)
         if (off + 4 <= src_bytes) {
             unsigned v;
@@ -372,24 +382,14 @@ __device__ __forceinline__ void letterbox_pixels4(const uint8_t *frames, size_t 
         }
         return (unsigned)frames[off] | ((unsigned)frames[off + 1] << 8) | ((unsigned)frames[off + 2] << 16);
     };
-    auto coeff = [](int d, double scale, int n, int &s0, int &s1, int &a0, int &a1) {
-        float f = (float)(((double)d + 0.5) * scale - 0.5);
-        int s = (int)floorf(f);
-        f -= (float)s;
-        if (s < 0) { s = 0; f = 0.f; }
-        if (s >= n - 1) { s = n - 1; f = 0.f; }
-        s0 = s; s1 = min(s + 1, n - 1);
-        a1 = (int)rintf(__fmul_rn(f, 2048.f));
-        a0 = (int)rintf(__fmul_rn(__fsub_rn(1.f, f), 2048.f));
-    };
     int sy0 = 0, sy1 = 0, b0 = 0, b1 = 0;
-    if (y < new_h) coeff(y, scale_y, H, sy0, sy1, b0, b1);
+    if (y < new_h) resize_coeff(y, scale_y, H, sy0, sy1, b0, b1);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const int x = x4 + i;
         if (x >= new_w || y >= new_h) { px[3 * i] = px[3 * i + 1] = px[3 * i + 2] = 0; continue; }
         int sx0, sx1, a0, a1;
-        coeff(x, scale_x, W, sx0, sx1, a0, a1);
+        resize_coeff(x, scale_x, W, sx0, sx1, a0, a1);
         const unsigned p00 = fetch(fbase + ((size_t)sy0 * ld + sx0) * 3), p01 = fetch(fbase + ((size_t)sy0 * ld + sx1) * 3);
         const unsigned p10 = fetch(fbase + ((size_t)sy1 * ld + sx0) * 3), p11 = fetch(fbase + ((size_t)sy1 * ld + sx1) * 3);
 #pragma unroll
@@ -397,12 +397,10 @@ __device__ __forceinline__ void letterbox_pixels4(const uint8_t *frames, size_t 
             const int T0 = (int)((p00 >> (8 * c)) & 255u) * a0 + (int)((p01 >> (8 * c)) & 255u) * a1;
             const int T1 = (int)((p10 >> (8 * c)) & 255u) * a0 + (int)((p11 >> (8 * c)) & 255u) * a1;
             const int v = (((b0 * (T0 >> 4)) >> 16) + ((b1 * (T1 >> 4)) >> 16) + 2) >> 2;
-            px[3 * i + c] = (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
+            px[3 * i + c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
         }
     }
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-        o[j] = (unsigned)px[4 * j] | ((unsigned)px[4 * j + 1] << 8) | ((unsigned)px[4 * j + 2] << 16) | ((unsigned)px[4 * j + 3] << 24);
+    store_quad(px, o);
 }
 
 __global__ void __launch_bounds__(256) letterbox_kernel4(const uint8_t *frames, int H, int W, uint8_t *out, int in_h, int in_w, int new_h, int new_w,
@@ -434,34 +432,13 @@ __global__ void __launch_bounds__(256) letterbox_kernel4_ragged(const uint8_t *f
 // ---- tiled detection (fid_tile_cut): tile blockIdx.z of the table is cut from its frame into its own detector input ----
 // A native tile (kind 0) is the rectangle copied to the top-left corner, the rest zero; a letterboxed one (kind 1) is letterbox_pixel /
 // letterbox_pixels4 on the rectangle, whose rows are W pixels apart.  Only bytes of pixels inside the rectangle are read, except the
-// guarded 4-byte fetch of letterbox_pixels4, which stays inside the frame batch.
-__global__ void __launch_bounds__(256) tile_cut_kernel(const uint8_t *frames, int H, int W, const fid::TileEntry *tab, uint8_t *out, int in_h, int in_w) {
-    const int t = blockIdx.z;
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= in_w) return;
-    const fid::TileEntry g = tab[t];
-    const uint8_t *src = frames + (((size_t)g.frame * H + g.y0) * W + g.x0) * 3;
-    // (kind 0: new_h x new_w == h x w, which letterbox_pixel copies 1:1 and pads with zeros)
-    letterbox_pixel(BgrSrc{src, W}, g.h, g.w, out + (((size_t)t * in_h + y) * in_w + x) * 3, x, y, g.new_h, g.new_w, g.scale_x, g.scale_y,
-                    g.mode == 2);
-}
-
-// the same cut from NV12 frames: the rectangle's pixels are addressed in FRAME coordinates, so an odd (x0, y0) keeps the frame's chroma grid
-__global__ void __launch_bounds__(256) tile_cut_kernel_nv12(Nv12Batch nv, const fid::TileEntry *tab, uint8_t *out, int in_h, int in_w) {
-    const int t = blockIdx.z;
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= in_w) return;
-    const fid::TileEntry g = tab[t];
-    letterbox_pixel(nv.frame(g.frame, g.x0, g.y0), g.h, g.w, out + (((size_t)t * in_h + y) * in_w + x) * 3, x, y, g.new_h, g.new_w, g.scale_x,
-                    g.scale_y, g.mode == 2);
-}
-
+// guarded 4-byte fetch of letterbox_pixels4, which stays inside the frame batch.  The one-pixel form is letterbox_kernel over TileGeom.
 __global__ void __launch_bounds__(256) tile_cut_kernel4_nv12(Nv12Batch nv, const fid::TileEntry *tab, uint8_t *out, int in_h, int in_w) {
     const int t = blockIdx.z;
     const int x4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, y = blockIdx.y;
     if (x4 >= in_w) return;
     const fid::TileEntry g = tab[t];
-    letterbox_quad(nv.frame(g.frame, g.x0, g.y0), g.h, g.w, (unsigned *)(out + (((size_t)t * in_h + y) * in_w + x4) * 3), x4, y, g.new_h, g.new_w,
+    letterbox_quad(nv.frame(g.frame, g.x0, g.y0).src, g.h, g.w, (unsigned *)(out + (((size_t)t * in_h + y) * in_w + x4) * 3), x4, y, g.new_h, g.new_w,
                    g.scale_x, g.scale_y, g.mode == 2);
 }
 
@@ -524,8 +501,37 @@ int nv12_batch(const uint8_t *nv12, const fid_nv12_desc *desc, int B, int H, int
                 desc ? desc->pitch : 0, desc ? (long long)desc->uv_offset : 0ll, desc ? (long long)desc->frame_stride : 0ll,
                 desc ? desc->standard : 0);
     nv->p = nv12; nv->frame_stride = desc->frame_stride; nv->uv_offset = desc->uv_offset; nv->pitch = desc->pitch;
+    nv->H = H; nv->W = W;
     fid_yuv_coeffs_for(desc->standard, &nv->k);
     return FID_OK;
+}
+
+// The device table of a batch that has one (under the context's lock, before the launch): the host's n entries in, the device's out.
+template <class Frames>
+int upload_table(fid_ctx *, Frames &, int) { return FID_OK; }
+int upload_table(fid_ctx *ctx, RaggedBatch &frames, int n) { return fid::ragged_table(ctx, frames.tab, n, &frames.tab); }
+
+// Launch tail of the six fid_align_crops* entry points, which have validated every argument: n_rows crops from a batch of B frames.
+template <class Frames, class Rows>
+int launch_warp(fid_ctx *ctx, Frames frames, int B, Rows rows, int n_rows, const float *kps_dev, uint8_t *crops_dev, double *M_dev) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
+    FID_TRY(upload_table(ctx, frames, B));
+    hipLaunchKernelGGL((align_warp<Frames, Rows>), dim3(OUT / ROWS_PER_BLOCK, n_rows), dim3(256), 0, ctx->stream, frames, rows, kps_dev, crops_dev,
+                       M_dev);
+    FID_HIP(hipGetLastError());
+    return FID_OK;
+}
+
+// The four-pixel kernels write aligned dwords: whole quads per row, on an aligned output.
+inline bool quads_fit(int in_w, const uint8_t *out_dev) { return in_w % 4 == 0 && ((size_t)out_dev & 3) == 0; }
+inline dim3 quad_grid(int in_w, int in_h, int n) { return dim3(fid::cdiv(in_w / 4, 256), in_h, n); }
+
+// The one-pixel letterbox kernel over n images (or tiles), enqueued by an entry point that holds the context's lock.
+template <class Frames, class Geom>
+void launch_letterbox(fid_ctx *ctx, const Frames &frames, const Geom &geom, int n, uint8_t *out_dev, int in_h, int in_w) {
+    hipLaunchKernelGGL((letterbox_kernel<Frames, Geom>), dim3(fid::cdiv(in_w, 256), in_h, n), dim3(256), 0, ctx->stream, frames, geom, out_dev, in_h,
+                       in_w);
 }
 
 }  // namespace
@@ -537,13 +543,7 @@ int fid_align_crops(fid_ctx *ctx, const uint8_t *frames_dev, int B, int H, int W
     FID_REQUIRE(ctx && frames_dev && kps_dev && counts_dev && crops_dev, "NULL argument");
     FID_REQUIRE(B > 0 && H > 0 && W > 0 && cap > 0 && faces_per_frame > 0, "bad sizes");
     FID_REQUIRE((long long)B * faces_per_frame <= 65535, "too many face slots per call (%lld)", (long long)B * faces_per_frame);
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
-    dim3 grid(OUT / ROWS_PER_BLOCK, B * faces_per_frame);
-    hipLaunchKernelGGL(align_warp, grid, dim3(256), 0, ctx->stream, frames_dev, H, W, kps_dev, counts_dev, cap,
-                       faces_per_frame, crops_dev, M_dev);
-    FID_HIP(hipGetLastError());
-    return FID_OK;
+    return launch_warp(ctx, BgrBatch{frames_dev, H, W}, B, SlotRows{counts_dev, cap, faces_per_frame}, B * faces_per_frame, kps_dev, crops_dev, M_dev);
 }
 
 int fid_align_crops_packed(fid_ctx *ctx, const uint8_t *frames_dev, int B, int H, int W, const float *kps_dev, int cap,
@@ -552,39 +552,23 @@ int fid_align_crops_packed(fid_ctx *ctx, const uint8_t *frames_dev, int B, int H
     FID_REQUIRE(B > 0 && H > 0 && W > 0 && cap > 0 && n_rows > 0, "bad sizes");
     FID_REQUIRE((long long)B * cap <= 0x7FFFFFFFll, "B * cap = %lld overflows the row table's int32 entries", (long long)B * cap);
     FID_REQUIRE(n_rows <= 65535, "too many face rows per call (%d)", n_rows);
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
-    dim3 grid(OUT / ROWS_PER_BLOCK, n_rows);
-    hipLaunchKernelGGL(align_warp_packed, grid, dim3(256), 0, ctx->stream, frames_dev, B, H, W, kps_dev, cap, src_dev, crops_dev, M_dev);
-    FID_HIP(hipGetLastError());
-    return FID_OK;
+    return launch_warp(ctx, BgrBatch{frames_dev, H, W}, B, PackedRows{src_dev, B, cap}, n_rows, kps_dev, crops_dev, M_dev);
 }
 
 int fid_letterbox(fid_ctx *ctx, const uint8_t *frames_dev, int B, int H, int W, uint8_t *out_dev, int in_h, int in_w,
                   double *det_scale) {
     FID_REQUIRE(ctx && frames_dev && out_dev, "NULL argument");
     FID_REQUIRE(B > 0 && H > 0 && W > 0 && in_h > 0 && in_w > 0 && B <= 65535 && in_h <= 65535, "bad sizes");
-    // scrfd.py:125-134 in double, int() truncation
-    const double im_ratio = (double)H / (double)W, model_ratio = (double)in_h / (double)in_w;
-    int new_h, new_w;
-    if (im_ratio > model_ratio) { new_h = in_h; new_w = (int)((double)new_h / im_ratio); }
-    else { new_w = in_w; new_h = (int)((double)new_w * im_ratio); }
-    FID_REQUIRE(new_h > 0 && new_w > 0, "degenerate letterbox %dx%d", new_w, new_h);
-    if (det_scale) *det_scale = (double)new_h / (double)H;
+    fid::RaggedImg g{};
+    FID_REQUIRE(fid::ragged_geometry(H, W, in_h, in_w, &g), "degenerate letterbox %dx%d", g.new_w, g.new_h);
+    if (det_scale) *det_scale = (double)g.new_h / (double)H;
     std::lock_guard<std::mutex> lk(ctx->mu);
     FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
-    dim3 grid(fid::cdiv(in_w, 256), in_h, B);
-    const int area2x = (W == 2 * new_w && H == 2 * new_h) ? 1 : 0;
-    static const bool lb_bytes = getenv("FID_LETTERBOX_BYTES") != nullptr;      // A/B: the one-pixel-per-thread kernel everywhere
-    if (!lb_bytes && !area2x && !(new_w == W && new_h == H) && in_w % 4 == 0 && ((size_t)out_dev & 3) == 0) {
-        dim3 grid4(fid::cdiv(in_w / 4, 256), in_h, B);
-        hipLaunchKernelGGL(letterbox_kernel4, grid4, dim3(256), 0, ctx->stream, frames_dev, H, W, out_dev, in_h, in_w, new_h, new_w,
-                           (double)W / (double)new_w, (double)H / (double)new_h, (size_t)B * H * W * 3);
-        FID_HIP(hipGetLastError());
-        return FID_OK;
-    }
-    hipLaunchKernelGGL(letterbox_kernel, grid, dim3(256), 0, ctx->stream, frames_dev, H, W, out_dev, in_h, in_w, new_h, new_w,
-                       (double)W / (double)new_w, (double)H / (double)new_h, area2x);
+    if (g.mode == 0 && quads_fit(in_w, out_dev))
+        hipLaunchKernelGGL(letterbox_kernel4, quad_grid(in_w, in_h, B), dim3(256), 0, ctx->stream, frames_dev, H, W, out_dev, in_h, in_w, g.new_h,
+                           g.new_w, g.scale_x, g.scale_y, (size_t)B * H * W * 3);
+    else
+        launch_letterbox(ctx, BgrBatch{frames_dev, H, W}, UniformGeom{g.new_h, g.new_w, g.scale_x, g.scale_y, g.mode == 2}, B, out_dev, in_h, in_w);
     FID_HIP(hipGetLastError());
     return FID_OK;
 }
@@ -599,13 +583,11 @@ int fid_tile_cut(fid_ctx *ctx, const uint8_t *frames_dev, int B, int H, int W, c
     FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
     const fid::TileEntry *tab;
     FID_TRY(fid::tile_table(ctx, host.data(), T, &tab));
-    if (in_w % 4 == 0 && ((size_t)out_dev & 3) == 0) {
-        dim3 grid4(fid::cdiv(in_w / 4, 256), in_h, T);
-        hipLaunchKernelGGL(tile_cut_kernel4, grid4, dim3(256), 0, ctx->stream, frames_dev, H, W, tab, out_dev, in_h, in_w, (size_t)B * H * W * 3);
-    } else {
-        dim3 grid(fid::cdiv(in_w, 256), in_h, T);
-        hipLaunchKernelGGL(tile_cut_kernel, grid, dim3(256), 0, ctx->stream, frames_dev, H, W, tab, out_dev, in_h, in_w);
-    }
+    if (quads_fit(in_w, out_dev))
+        hipLaunchKernelGGL(tile_cut_kernel4, quad_grid(in_w, in_h, T), dim3(256), 0, ctx->stream, frames_dev, H, W, tab, out_dev, in_h, in_w,
+                           (size_t)B * H * W * 3);
+    else
+        launch_letterbox(ctx, BgrBatch{frames_dev, H, W}, TileGeom{tab}, T, out_dev, in_h, in_w);
     FID_HIP(hipGetLastError());
     return FID_OK;
 }
@@ -621,16 +603,13 @@ int fid_letterbox_ragged(fid_ctx *ctx, const uint8_t *frames_dev, size_t frames_
         for (int b = 0; b < B; b++) det_scale[b] = (double)host[b].new_h / (double)host[b].H;
     std::lock_guard<std::mutex> lk(ctx->mu);
     FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
-    const fid::RaggedImg *tab;
-    FID_TRY(fid::ragged_table(ctx, host.data(), B, &tab));
-    static const bool lb_bytes = getenv("FID_LETTERBOX_BYTES") != nullptr;      // A/B: the one-pixel-per-thread kernel everywhere
-    if (!lb_bytes && in_w % 4 == 0 && ((size_t)out_dev & 3) == 0) {
-        dim3 grid4(fid::cdiv(in_w / 4, 256), in_h, B);
-        hipLaunchKernelGGL(letterbox_kernel4_ragged, grid4, dim3(256), 0, ctx->stream, frames_dev, tab, out_dev, in_h, in_w, frames_bytes);
-    } else {
-        dim3 grid(fid::cdiv(in_w, 256), in_h, B);
-        hipLaunchKernelGGL(letterbox_kernel_ragged, grid, dim3(256), 0, ctx->stream, frames_dev, tab, out_dev, in_h, in_w);
-    }
+    RaggedBatch frames{frames_dev, host.data()};
+    FID_TRY(upload_table(ctx, frames, B));
+    if (quads_fit(in_w, out_dev))
+        hipLaunchKernelGGL(letterbox_kernel4_ragged, quad_grid(in_w, in_h, B), dim3(256), 0, ctx->stream, frames_dev, frames.tab, out_dev, in_h, in_w,
+                           frames_bytes);
+    else
+        launch_letterbox(ctx, frames, RaggedGeom{}, B, out_dev, in_h, in_w);
     FID_HIP(hipGetLastError());
     return FID_OK;
 }
@@ -642,15 +621,8 @@ int fid_align_crops_ragged(fid_ctx *ctx, const uint8_t *frames_dev, size_t frame
     FID_REQUIRE((long long)B * faces_per_frame <= 65535, "too many face slots per call (%lld)", (long long)B * faces_per_frame);
     std::vector<fid::RaggedImg> host;
     FID_TRY(ragged_entries(hw, offsets, frames_bytes, B, 0, 0, host));
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
-    const fid::RaggedImg *tab;
-    FID_TRY(fid::ragged_table(ctx, host.data(), B, &tab));
-    dim3 grid(OUT / ROWS_PER_BLOCK, B * faces_per_frame);
-    hipLaunchKernelGGL(align_warp_ragged, grid, dim3(256), 0, ctx->stream, frames_dev, tab, kps_dev, counts_dev, cap, faces_per_frame, crops_dev,
-                       M_dev);
-    FID_HIP(hipGetLastError());
-    return FID_OK;
+    return launch_warp(ctx, RaggedBatch{frames_dev, host.data()}, B, SlotRows{counts_dev, cap, faces_per_frame}, B * faces_per_frame, kps_dev,
+                       crops_dev, M_dev);
 }
 
 int fid_align_crops_packed_ragged(fid_ctx *ctx, const uint8_t *frames_dev, size_t frames_bytes, const int32_t *hw, const int64_t *offsets, int B,
@@ -661,14 +633,7 @@ int fid_align_crops_packed_ragged(fid_ctx *ctx, const uint8_t *frames_dev, size_
     FID_REQUIRE(n_rows <= 65535, "too many face rows per call (%d)", n_rows);
     std::vector<fid::RaggedImg> host;
     FID_TRY(ragged_entries(hw, offsets, frames_bytes, B, 0, 0, host));
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
-    const fid::RaggedImg *tab;
-    FID_TRY(fid::ragged_table(ctx, host.data(), B, &tab));
-    dim3 grid(OUT / ROWS_PER_BLOCK, n_rows);
-    hipLaunchKernelGGL(align_warp_packed_ragged, grid, dim3(256), 0, ctx->stream, frames_dev, tab, B, kps_dev, cap, src_dev, crops_dev, M_dev);
-    FID_HIP(hipGetLastError());
-    return FID_OK;
+    return launch_warp(ctx, RaggedBatch{frames_dev, host.data()}, B, PackedRows{src_dev, B, cap}, n_rows, kps_dev, crops_dev, M_dev);
 }
 
 // ---- NV12 frames (include/faceid.h): the conversion alone, both ways, and the four frame readers with the conversion fused into their taps ----
@@ -688,7 +653,7 @@ int fid_nv12_to_bgr(fid_ctx *ctx, const uint8_t *nv12_dev, const fid_nv12_desc *
     std::lock_guard<std::mutex> lk(ctx->mu);
     FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
     dim3 grid(fid::cdiv(W / 2, 256), H, B);
-    hipLaunchKernelGGL(nv12_to_bgr_kernel, grid, dim3(256), 0, ctx->stream, nv, H, W, bgr_out_dev);
+    hipLaunchKernelGGL(nv12_to_bgr_kernel, grid, dim3(256), 0, ctx->stream, nv, bgr_out_dev);
     FID_HIP(hipGetLastError());
     return FID_OK;
 }
@@ -729,15 +694,13 @@ int fid_letterbox_nv12(fid_ctx *ctx, const uint8_t *nv12_dev, const fid_nv12_des
     FID_REQUIRE(B > 0 && H > 0 && W > 0 && in_h > 0 && in_w > 0 && B <= 65535 && in_h <= 65535, "bad sizes");
     Nv12Batch nv;
     FID_TRY(nv12_batch(nv12_dev, desc, B, H, W, &nv));
-    fid::RaggedImg g{};                             // fid_letterbox's geometry: the same expressions in double
+    fid::RaggedImg g{};
     FID_REQUIRE(fid::ragged_geometry(H, W, in_h, in_w, &g), "degenerate letterbox %dx%d", g.new_w, g.new_h);
     if (det_scale) *det_scale = (double)g.new_h / (double)H;
     std::lock_guard<std::mutex> lk(ctx->mu);
     FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
     // (one output pixel per thread: with four, 32 frames of 1080p -> 640x640 took 0.053 instead of 0.048 ms -- docs/FINDINGS.md)
-    dim3 grid(fid::cdiv(in_w, 256), in_h, B);
-    hipLaunchKernelGGL(letterbox_kernel_nv12, grid, dim3(256), 0, ctx->stream, nv, H, W, out_dev, in_h, in_w, g.new_h, g.new_w, g.scale_x,
-                       g.scale_y, g.mode == 2 ? 1 : 0);
+    launch_letterbox(ctx, nv, UniformGeom{g.new_h, g.new_w, g.scale_x, g.scale_y, g.mode == 2}, B, out_dev, in_h, in_w);
     FID_HIP(hipGetLastError());
     return FID_OK;
 }
@@ -754,13 +717,10 @@ int fid_tile_cut_nv12(fid_ctx *ctx, const uint8_t *nv12_dev, const fid_nv12_desc
     FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
     const fid::TileEntry *tab;
     FID_TRY(fid::tile_table(ctx, host.data(), T, &tab));
-    if (in_w % 4 == 0 && ((size_t)out_dev & 3) == 0) {
-        dim3 grid4(fid::cdiv(in_w / 4, 256), in_h, T);
-        hipLaunchKernelGGL(tile_cut_kernel4_nv12, grid4, dim3(256), 0, ctx->stream, nv, tab, out_dev, in_h, in_w);
-    } else {
-        dim3 grid(fid::cdiv(in_w, 256), in_h, T);
-        hipLaunchKernelGGL(tile_cut_kernel_nv12, grid, dim3(256), 0, ctx->stream, nv, tab, out_dev, in_h, in_w);
-    }
+    if (quads_fit(in_w, out_dev))
+        hipLaunchKernelGGL(tile_cut_kernel4_nv12, quad_grid(in_w, in_h, T), dim3(256), 0, ctx->stream, nv, tab, out_dev, in_h, in_w);
+    else
+        launch_letterbox(ctx, nv, TileGeom{tab}, T, out_dev, in_h, in_w);
     FID_HIP(hipGetLastError());
     return FID_OK;
 }
@@ -772,12 +732,7 @@ int fid_align_crops_nv12(fid_ctx *ctx, const uint8_t *nv12_dev, const fid_nv12_d
     FID_REQUIRE((long long)B * faces_per_frame <= 65535, "too many face slots per call (%lld)", (long long)B * faces_per_frame);
     Nv12Batch nv;
     FID_TRY(nv12_batch(nv12_dev, desc, B, H, W, &nv));
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
-    dim3 grid(OUT / ROWS_PER_BLOCK, B * faces_per_frame);
-    hipLaunchKernelGGL(align_warp_nv12, grid, dim3(256), 0, ctx->stream, nv, H, W, kps_dev, counts_dev, cap, faces_per_frame, crops_dev, M_dev);
-    FID_HIP(hipGetLastError());
-    return FID_OK;
+    return launch_warp(ctx, nv, B, SlotRows{counts_dev, cap, faces_per_frame}, B * faces_per_frame, kps_dev, crops_dev, M_dev);
 }
 
 int fid_align_crops_packed_nv12(fid_ctx *ctx, const uint8_t *nv12_dev, const fid_nv12_desc *desc, int B, int H, int W, const float *kps_dev,
@@ -788,12 +743,7 @@ int fid_align_crops_packed_nv12(fid_ctx *ctx, const uint8_t *nv12_dev, const fid
     FID_REQUIRE(n_rows <= 65535, "too many face rows per call (%d)", n_rows);
     Nv12Batch nv;
     FID_TRY(nv12_batch(nv12_dev, desc, B, H, W, &nv));
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
-    dim3 grid(OUT / ROWS_PER_BLOCK, n_rows);
-    hipLaunchKernelGGL(align_warp_packed_nv12, grid, dim3(256), 0, ctx->stream, nv, B, H, W, kps_dev, cap, src_dev, crops_dev, M_dev);
-    FID_HIP(hipGetLastError());
-    return FID_OK;
+    return launch_warp(ctx, nv, B, PackedRows{src_dev, B, cap}, n_rows, kps_dev, crops_dev, M_dev);
 }
 
 }  // extern "C"

@@ -121,16 +121,18 @@ struct RaggedImg {
     int mode;                   // letterbox: 0 bilinear, 1 identity copy, 2 exact 2x decimation (INTER_AREA)
 };
 static_assert(sizeof(RaggedImg) == 48, "RaggedImg is copied to the device as 48-byte entries");
-// letterbox geometry of one H x W image into in_h x in_w (scrfd.py:125-134 in double, int() truncation); false = degenerate
+// Letterbox geometry of one H x W image into in_h x in_w (scrfd.py:125-134 in double, int() truncation); false = degenerate.  The one
+// statement of it: every letterbox, tile cut and post-process entry point takes its sizes, scales, det_scale and mode from here.  A
+// degenerate image still gets its sizes and det_scale (fid_scrfd_postprocess refuses nothing and divides by it, as the reference does).
 inline bool ragged_geometry(int H, int W, int in_h, int in_w, RaggedImg *g) {
     const double im_ratio = (double)H / (double)W, model_ratio = (double)in_h / (double)in_w;
     int new_h, new_w;
     if (im_ratio > model_ratio) { new_h = in_h; new_w = (int)((double)new_h / im_ratio); }
     else { new_w = in_w; new_h = (int)((double)new_w * im_ratio); }
     g->H = H; g->W = W; g->new_h = new_h; g->new_w = new_w;
+    g->det_scale = (float)((double)new_h / (double)H);
     if (new_h <= 0 || new_w <= 0) return false;
     g->scale_x = (double)W / (double)new_w; g->scale_y = (double)H / (double)new_h;
-    g->det_scale = (float)((double)new_h / (double)H);
     g->mode = (new_w == W && new_h == H) ? 1 : ((W == 2 * new_w && H == 2 * new_h) ? 2 : 0);
     return true;
 }

@@ -21,6 +21,18 @@ struct HeadViews {
     int anc_stride[9];
     long long batch_stride[9];
 };
+// the kernel argument from an entry point's four arrays of nine (the arrays themselves non-NULL: checked by the caller)
+int head_views(const float *const head_dev[9], const int32_t pix_stride[9], const int32_t anc_stride[9], const int64_t batch_stride[9],
+               HeadViews *hv) {
+    for (int k = 0; k < 9; k++) {
+        FID_REQUIRE(head_dev[k], "head %d is NULL", k);
+        hv->ptr[k] = head_dev[k];
+        hv->pix_stride[k] = pix_stride[k];
+        hv->anc_stride[k] = anc_stride[k];
+        hv->batch_stride[k] = batch_stride[k];
+    }
+    return FID_OK;
+}
 
 // (-0.0 takes +0.0's key: numpy's sort compares the two equal and leaves them in index order)
 __device__ __forceinline__ unsigned sortable(float f) {
@@ -28,74 +40,45 @@ __device__ __forceinline__ unsigned sortable(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-// One thread per anchor.  scrfd.py:89-119 + :145-148 (the division by det_scale).  The body is shared by the uniform kernel and the
-// mixed-size one, which differ only in where frame b's det_scale comes from.
-__device__ __forceinline__ void decode_compact_frame(const HeadViews &hv, int b, int in_h, int in_w, int A, float thr, float det_scale,
-                                                     int by_index, int cand_cap, int *cand_count, unsigned long long *cand_key,
-                                                     float *cand_data) {
-    const int n8 = (in_h / 8) * (in_w / 8) * A, n16 = (in_h / 16) * (in_w / 16) * A,
-              n32 = (in_h / 32) * (in_w / 32) * A;
-    int g = blockIdx.x * blockDim.x + threadIdx.x;  // flat anchor index over the 3 levels
-    if (g >= n8 + n16 + n32) return;
-    int lvl, i, stride;
-    if (g < n8) { lvl = 0; i = g; stride = 8; }
-    else if (g < n8 + n16) { lvl = 1; i = g - n8; stride = 16; }
-    else { lvl = 2; i = g - n8 - n16; stride = 32; }
-    const int pix = i / A, a = i - pix * A;
-    const float score = hv.ptr[lvl][b * hv.batch_stride[lvl] + (long long)pix * hv.pix_stride[lvl] + a * hv.anc_stride[lvl]];
-    if (!(score >= thr)) return;
-    const int slot = atomicAdd(&cand_count[b], 1);
-    if (slot >= cand_cap) return;  // overflow is reported through the count itself
-    const int fw = in_w / stride;
-    const float cx = (float)((pix % fw) * stride), cy = (float)((pix / fw) * stride);
-    const float fs = (float)stride;
-    const float *bp = hv.ptr[3 + lvl] + b * hv.batch_stride[3 + lvl] + (long long)pix * hv.pix_stride[3 + lvl] + a * hv.anc_stride[3 + lvl];
-    const float *kp = hv.ptr[6 + lvl] + b * hv.batch_stride[6 + lvl] + (long long)pix * hv.pix_stride[6 + lvl] + a * hv.anc_stride[6 + lvl];
-    float *o = cand_data + ((size_t)b * cand_cap + slot) * CAND_W;
-    // distance2bbox on (pred * stride), then / det_scale
-    o[0] = __fdiv_rn(__fsub_rn(cx, __fmul_rn(bp[0], fs)), det_scale);
-    o[1] = __fdiv_rn(__fsub_rn(cy, __fmul_rn(bp[1], fs)), det_scale);
-    o[2] = __fdiv_rn(__fadd_rn(cx, __fmul_rn(bp[2], fs)), det_scale);
-    o[3] = __fdiv_rn(__fadd_rn(cy, __fmul_rn(bp[3], fs)), det_scale);
-    o[4] = score;
-#pragma unroll
-    for (int k = 0; k < 5; k++) {
-        o[5 + 2 * k] = __fdiv_rn(__fadd_rn(cx, __fmul_rn(kp[2 * k], fs)), det_scale);
-        o[6 + 2 * k] = __fdiv_rn(__fadd_rn(cy, __fmul_rn(kp[2 * k + 1], fs)), det_scale);
+// Where the candidates of head batch entry t go, and what scales them: the placement policy of decode_compact.
+struct PlaceUniform {        // entry t is frame t; one det_scale for the batch.  by_index: anchor order instead of score order (fid_scrfd_decode)
+    static constexpr bool tiled = false;
+    float ds;
+    int by_index;
+    __device__ __forceinline__ float det_scale(int) const { return ds; }
+};
+struct PlaceRagged {         // a mixed-size batch: frame t's det_scale from the per-image table (block-uniform)
+    static constexpr bool tiled = false;
+    static constexpr int by_index = 0;
+    const fid::RaggedImg *tab;
+    __device__ __forceinline__ float det_scale(int t) const { return tab[t].det_scale; }
+};
+// Tiled detection: entry t is tile t of the table, its candidates join frame tab[t].frame's list in FRAME coordinates: every coordinate
+// moves by the tile's origin, (v / det_scale) + (float)x0 or y0, two single rounded fp32 operations.  A candidate whose frame box comes
+// within `margin` pixels of a side of the tile that is a cut (not the frame's boundary) is dropped before it takes a slot: the half face a
+// tile sees at a cut (margin < 0: no rule).  Order inside a frame: score descending, then (tile rank, anchor) ascending -- what
+// concatenating the tiles' candidate arrays in table order and the oracle's two stable sorts produce.
+struct PlaceTiled {
+    static constexpr bool tiled = true;
+    static constexpr int by_index = 0;
+    const fid::TileEntry *tab;
+    int img_h, img_w, margin;
+    __device__ __forceinline__ bool at_a_cut(const fid::TileEntry &e, const float (&xy)[4]) const {      // xy: the frame box x1 y1 x2 y2
+        if (margin < 0) return false;
+        return (e.x0 > 0 && xy[0] < (float)(e.x0 + margin)) || (e.y0 > 0 && xy[1] < (float)(e.y0 + margin)) ||
+               (e.x0 + e.w < img_w && xy[2] > (float)(e.x0 + e.w - margin)) || (e.y0 + e.h < img_h && xy[3] > (float)(e.y0 + e.h - margin));
     }
-    o[15] = __int_as_float(g);
-    // order: score descending, then flat anchor index ascending (what a stable argsort()[::-1]
-    // followed by nms()'s own stable argsort()[::-1] produces; identical to any order when tie-free)
-    cand_key[(size_t)b * cand_cap + slot] =
-        by_index ? ((unsigned long long)(~(unsigned)g) << 32) : (((unsigned long long)sortable(score) << 32) | (unsigned)(~(unsigned)g));
-}
+};
 
-__global__ void __launch_bounds__(256) decode_compact(HeadViews hv, int in_h, int in_w, int A, float thr,
-                                                      float det_scale, int by_index, int cand_cap, int *cand_count,
-                                                      unsigned long long *cand_key, float *cand_data) {
-    decode_compact_frame(hv, blockIdx.y, in_h, in_w, A, thr, det_scale, by_index, cand_cap, cand_count, cand_key, cand_data);
-}
-
-// a mixed-size batch: frame b's det_scale from the per-image table (block-uniform)
-__global__ void __launch_bounds__(256) decode_compact_ragged(HeadViews hv, int in_h, int in_w, int A, float thr, const fid::RaggedImg *tab,
-                                                             int cand_cap, int *cand_count, unsigned long long *cand_key, float *cand_data) {
-    decode_compact_frame(hv, blockIdx.y, in_h, in_w, A, thr, tab[blockIdx.y].det_scale, 0, cand_cap, cand_count, cand_key, cand_data);
-}
-
-// Tiled detection: head batch entry blockIdx.y is tile t of the table, its candidates join frame tab[t].frame's list in FRAME coordinates.
-// The decode is decode_compact_frame's, operation for operation; every coordinate then moves by the tile's origin,
-// (v / det_scale) + (float)x0 or y0, two single rounded fp32 operations.  A candidate whose frame box comes within `margin` pixels of a side
-// of the tile that is a cut (not the frame's boundary) is dropped before it takes a slot: the half face a tile sees at a cut (margin < 0: no
-// rule).  Order inside a frame: score descending, then (tile rank, anchor) ascending -- what concatenating the tiles' candidate arrays in table
-// order and the oracle's two stable sorts produce.
-__global__ void __launch_bounds__(256) decode_compact_tiled(HeadViews hv, int in_h, int in_w, int A, float thr, const fid::TileEntry *tab,
-                                                            int img_h, int img_w, int margin, int cand_cap, int *cand_count,
-                                                            unsigned long long *cand_key, float *cand_data) {
+// One thread per anchor.  scrfd.py:89-119 + :145-148 (the division by det_scale).  The untiled forms add no origin, not even 0.0f: that
+// would turn a -0.0 into +0.0.
+template <class Place>
+__global__ void __launch_bounds__(256) decode_compact(HeadViews hv, int in_h, int in_w, int A, float thr, Place place, int cand_cap,
+                                                      int *cand_count, unsigned long long *cand_key, float *cand_data) {
     const int n8 = (in_h / 8) * (in_w / 8) * A, n16 = (in_h / 16) * (in_w / 16) * A, n32 = (in_h / 32) * (in_w / 32) * A;
     const int g = blockIdx.x * blockDim.x + threadIdx.x;  // flat anchor index over the 3 levels
     if (g >= n8 + n16 + n32) return;
     const int t = blockIdx.y;
-    const fid::TileEntry e = tab[t];
     int lvl, i, stride;
     if (g < n8) { lvl = 0; i = g; stride = 8; }
     else if (g < n8 + n16) { lvl = 1; i = g - n8; stride = 16; }
@@ -103,35 +86,59 @@ __global__ void __launch_bounds__(256) decode_compact_tiled(HeadViews hv, int in
     const int pix = i / A, a = i - pix * A;
     const float score = hv.ptr[lvl][t * hv.batch_stride[lvl] + (long long)pix * hv.pix_stride[lvl] + a * hv.anc_stride[lvl]];
     if (!(score >= thr)) return;
+    int b = t;
+    unsigned idx = (unsigned)g;
+    float ds, ox = 0.f, oy = 0.f;
+    [[maybe_unused]] fid::TileEntry e;
+    if constexpr (Place::tiled) {
+        e = place.tab[t];
+        b = e.frame; ds = e.det_scale; ox = (float)e.x0; oy = (float)e.y0;
+        idx = (unsigned)e.rank * (unsigned)(n8 + n16 + n32) + (unsigned)g;   // < 2^31: checked by the launcher
+    } else {
+        ds = place.det_scale(t);
+    }
+    float *o = nullptr;                        // the candidate's record, once it has a slot
+    unsigned long long *key = nullptr;
+    auto take_slot = [&]() {
+        const int slot = atomicAdd(&cand_count[b], 1);
+        if (slot >= cand_cap) return false;    // overflow is reported through the count itself
+        o = cand_data + ((size_t)b * cand_cap + slot) * CAND_W;
+        key = cand_key + (size_t)b * cand_cap + slot;
+        return true;
+    };
     const int fw = in_w / stride;
     const float cx = (float)((pix % fw) * stride), cy = (float)((pix / fw) * stride);
-    const float fs = (float)stride, ds = e.det_scale, ox = (float)e.x0, oy = (float)e.y0;
+    const float fs = (float)stride;
     const float *bp = hv.ptr[3 + lvl] + t * hv.batch_stride[3 + lvl] + (long long)pix * hv.pix_stride[3 + lvl] + a * hv.anc_stride[3 + lvl];
-    const float X1 = __fadd_rn(__fdiv_rn(__fsub_rn(cx, __fmul_rn(bp[0], fs)), ds), ox);
-    const float Y1 = __fadd_rn(__fdiv_rn(__fsub_rn(cy, __fmul_rn(bp[1], fs)), ds), oy);
-    const float X2 = __fadd_rn(__fdiv_rn(__fadd_rn(cx, __fmul_rn(bp[2], fs)), ds), ox);
-    const float Y2 = __fadd_rn(__fdiv_rn(__fadd_rn(cy, __fmul_rn(bp[3], fs)), ds), oy);
-    if (margin >= 0) {
-        if (e.x0 > 0 && X1 < (float)(e.x0 + margin)) return;
-        if (e.y0 > 0 && Y1 < (float)(e.y0 + margin)) return;
-        if (e.x0 + e.w < img_w && X2 > (float)(e.x0 + e.w - margin)) return;
-        if (e.y0 + e.h < img_h && Y2 > (float)(e.y0 + e.h - margin)) return;
+    // distance2bbox / distance2kps on (pred * stride), then / det_scale
+    auto placed = [&](float v, float origin) { v = __fdiv_rn(v, ds); if constexpr (Place::tiled) v = __fadd_rn(v, origin); return v; };
+    auto box = [&](float *d) {
+        d[0] = placed(__fsub_rn(cx, __fmul_rn(bp[0], fs)), ox);
+        d[1] = placed(__fsub_rn(cy, __fmul_rn(bp[1], fs)), oy);
+        d[2] = placed(__fadd_rn(cx, __fmul_rn(bp[2], fs)), ox);
+        d[3] = placed(__fadd_rn(cy, __fmul_rn(bp[3], fs)), oy);
+    };
+    if constexpr (Place::tiled) {              // box -> margin test -> slot
+        float xy[4];
+        box(xy);
+        if (place.at_a_cut(e, xy)) return;
+        if (!take_slot()) return;
+        o[0] = xy[0]; o[1] = xy[1]; o[2] = xy[2]; o[3] = xy[3];
+    } else {                                   // slot -> box, each value stored as it is decoded (27 VGPRs; four divisions in flight take 35)
+        if (!take_slot()) return;
+        box(o);
     }
-    const int b = e.frame;
-    const int slot = atomicAdd(&cand_count[b], 1);
-    if (slot >= cand_cap) return;  // overflow is reported through the count itself
     const float *kp = hv.ptr[6 + lvl] + t * hv.batch_stride[6 + lvl] + (long long)pix * hv.pix_stride[6 + lvl] + a * hv.anc_stride[6 + lvl];
-    float *o = cand_data + ((size_t)b * cand_cap + slot) * CAND_W;
-    o[0] = X1; o[1] = Y1; o[2] = X2; o[3] = Y2;
     o[4] = score;
 #pragma unroll
     for (int k = 0; k < 5; k++) {
-        o[5 + 2 * k] = __fadd_rn(__fdiv_rn(__fadd_rn(cx, __fmul_rn(kp[2 * k], fs)), ds), ox);
-        o[6 + 2 * k] = __fadd_rn(__fdiv_rn(__fadd_rn(cy, __fmul_rn(kp[2 * k + 1], fs)), ds), oy);
+        o[5 + 2 * k] = placed(__fadd_rn(cx, __fmul_rn(kp[2 * k], fs)), ox);
+        o[6 + 2 * k] = placed(__fadd_rn(cy, __fmul_rn(kp[2 * k + 1], fs)), oy);
     }
-    const unsigned idx = (unsigned)e.rank * (unsigned)(n8 + n16 + n32) + (unsigned)g;   // < 2^31: checked by the launcher
     o[15] = __int_as_float((int)idx);
-    cand_key[(size_t)b * cand_cap + slot] = ((unsigned long long)sortable(score) << 32) | (unsigned)(~idx);
+    // order: score descending, then flat anchor index ascending (what a stable argsort()[::-1]
+    // followed by nms()'s own stable argsort()[::-1] produces; identical to any order when tie-free)
+    *key = place.by_index ? ((unsigned long long)(~idx) << 32) : (((unsigned long long)sortable(score) << 32) | (unsigned)(~idx));
 }
 
 // distance2bbox / distance2kps on plain arrays (utils/helpers.py:62-107): ncol = 4 -> bbox, else kps pairs
@@ -367,7 +374,7 @@ static void klog_nms(int cand_cap, int n_box) {
 }
 // shared by fid_scrfd_postprocess and the fused pipeline
 // tab != NULL: a mixed-size batch -- det_scale and the image size of frame b come from tab[b], img_h / img_w are unused
-// tiles != NULL: tiled detection -- the heads hold T tiles, whose candidates join the lists of the B frames they were cut from (decode_compact_tiled)
+// tiles != NULL: tiled detection -- the heads hold T tiles, whose candidates join the lists of the B frames they were cut from (PlaceTiled)
 int scrfd_postprocess_launch(fid_ctx *ctx, const HeadViews &hv, int B, int in_h, int in_w, int A, int img_h, int img_w,
                              float conf, float iou, int max_num, int metric, float *det_dev, float *kps_dev,
                              int32_t *counts_dev, int cap, const RaggedImg *tab = nullptr, const TileEntry *tiles = nullptr, int T = 0,
@@ -384,24 +391,18 @@ int scrfd_postprocess_launch(fid_ctx *ctx, const HeadViews &hv, int B, int in_h,
     auto *keys = (unsigned long long *)((char *)ws + off_keys);
     float *data = (float *)((char *)ws + off_data);
     float *sorted = (float *)((char *)ws + off_sorted);
-    // letterbox geometry in double, exactly as python does it (scrfd.py:123-134)
-    const double im_ratio = (double)img_h / (double)img_w;
-    const double model_ratio = (double)in_h / (double)in_w;
-    int new_h;
-    if (im_ratio > model_ratio) new_h = in_h;
-    else new_h = (int)((double)in_w * im_ratio);
-    const float det_scale = (float)((double)new_h / (double)img_h);
+    // (a degenerate letterbox is not refused here: its det_scale, 0.0f when new_h is 0, divides like the reference's)
+    RaggedImg geom{};
+    ragged_geometry(img_h, img_w, in_h, in_w, &geom);
     FID_HIP(hipMemsetAsync(cand_count, 0, (size_t)B * 4, ctx->stream));
     const int total_anchors = ((in_h / 8) * (in_w / 8) + (in_h / 16) * (in_w / 16) + (in_h / 32) * (in_w / 32)) * A;
-    dim3 g1(cdiv(total_anchors, 256), B);
-    if (tiles)
-        hipLaunchKernelGGL(decode_compact_tiled, dim3(g1.x, T), dim3(256), 0, ctx->stream, hv, in_h, in_w, A, conf, tiles, img_h, img_w, edge_margin,
-                           cc, cand_count, keys, data);
-    else if (tab)
-        hipLaunchKernelGGL(decode_compact_ragged, g1, dim3(256), 0, ctx->stream, hv, in_h, in_w, A, conf, tab, cc, cand_count, keys, data);
-    else
-        hipLaunchKernelGGL(decode_compact, g1, dim3(256), 0, ctx->stream, hv, in_h, in_w, A, conf, det_scale, 0, cc, cand_count,
-                           keys, data);
+    auto decode = [&](auto place, int n) {       // n head batch entries
+        hipLaunchKernelGGL(decode_compact<decltype(place)>, dim3(cdiv(total_anchors, 256), n), dim3(256), 0, ctx->stream, hv, in_h, in_w, A, conf,
+                           place, cc, cand_count, keys, data);
+    };
+    if (tiles) decode(PlaceTiled{tiles, img_h, img_w, edge_margin}, T);
+    else if (tab) decode(PlaceRagged{tab}, B);
+    else decode(PlaceUniform{geom.det_scale, 0}, B);
     dim3 g2(cdiv(cc, 256), B);
     hipLaunchKernelGGL(rank_scatter, g2, dim3(256), 0, ctx->stream, cand_count, keys, data, sorted, cc);
     int n_box = 0;
@@ -442,13 +443,7 @@ int fid_scrfd_postprocess(fid_ctx *ctx, const float *const head_dev[9], const in
     FID_REQUIRE(img_h > 0 && img_w > 0 && num_anchors > 0, "bad image size / anchors");
     FID_REQUIRE(metric == 0 || metric == 1, "metric must be 0 (max) or 1 (default)");
     HeadViews hv;
-    for (int k = 0; k < 9; k++) {
-        FID_REQUIRE(head_dev[k], "head %d is NULL", k);
-        hv.ptr[k] = head_dev[k];
-        hv.pix_stride[k] = pix_stride[k];
-        hv.anc_stride[k] = anc_stride[k];
-        hv.batch_stride[k] = batch_stride[k];
-    }
+    FID_TRY(head_views(head_dev, pix_stride, anc_stride, batch_stride, &hv));
     std::lock_guard<std::mutex> lk(ctx->mu);
     FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
     FID_TRY(fid::ensure_dyn_lds(ctx, (const void *)nms_select, (int)fid::nms_lds_bytes(ctx->cand_cap, nullptr)));   // (above 64 KB from ~2000 candidates on)
@@ -467,13 +462,7 @@ int fid_scrfd_postprocess_ragged(fid_ctx *ctx, const float *const head_dev[9], c
     FID_REQUIRE(num_anchors > 0, "bad anchors");
     FID_REQUIRE(metric == 0 || metric == 1, "metric must be 0 (max) or 1 (default)");
     HeadViews hv;
-    for (int k = 0; k < 9; k++) {
-        FID_REQUIRE(head_dev[k], "head %d is NULL", k);
-        hv.ptr[k] = head_dev[k];
-        hv.pix_stride[k] = pix_stride[k];
-        hv.anc_stride[k] = anc_stride[k];
-        hv.batch_stride[k] = batch_stride[k];
-    }
+    FID_TRY(head_views(head_dev, pix_stride, anc_stride, batch_stride, &hv));
     std::vector<fid::RaggedImg> host(B);
     for (int b = 0; b < B; b++) {
         FID_REQUIRE(hw[2 * b] > 0 && hw[2 * b + 1] > 0, "image %d: bad size %dx%d", b, hw[2 * b + 1], hw[2 * b]);
@@ -502,13 +491,7 @@ int fid_scrfd_postprocess_tiled(fid_ctx *ctx, const float *const head_dev[9], co
     FID_REQUIRE(img_h > 0 && img_w > 0 && num_anchors > 0, "bad image size / anchors");
     FID_REQUIRE(metric == 0 || metric == 1, "metric must be 0 (max) or 1 (default)");
     HeadViews hv;
-    for (int k = 0; k < 9; k++) {
-        FID_REQUIRE(head_dev[k], "head %d is NULL", k);
-        hv.ptr[k] = head_dev[k];
-        hv.pix_stride[k] = pix_stride[k];
-        hv.anc_stride[k] = anc_stride[k];
-        hv.batch_stride[k] = batch_stride[k];
-    }
+    FID_TRY(head_views(head_dev, pix_stride, anc_stride, batch_stride, &hv));
     std::vector<fid::TileEntry> host;
     int per_frame = 0;
     FID_TRY(fid::tile_entries(tiles, T, B, img_h, img_w, in_h, in_w, host, &per_frame));
@@ -532,10 +515,7 @@ int fid_scrfd_decode(fid_ctx *ctx, const float *const head_dev[9], const int32_t
     FID_REQUIRE(ctx && head_dev && pix_stride && anc_stride && batch_stride && rec_dev && counts_dev, "NULL argument");
     FID_REQUIRE(B > 0 && in_h > 0 && in_w > 0 && in_h % 32 == 0 && in_w % 32 == 0 && num_anchors > 0, "bad sizes");
     HeadViews hv;
-    for (int k = 0; k < 9; k++) {
-        FID_REQUIRE(head_dev[k], "head %d is NULL", k);
-        hv.ptr[k] = head_dev[k]; hv.pix_stride[k] = pix_stride[k]; hv.anc_stride[k] = anc_stride[k]; hv.batch_stride[k] = batch_stride[k];
-    }
+    FID_TRY(head_views(head_dev, pix_stride, anc_stride, batch_stride, &hv));
     std::lock_guard<std::mutex> lk(ctx->mu);
     FID_HIP(hipSetDevice(ctx->device));            // (a thread may drive contexts on several devices)
     const int cc = ctx->cand_cap;
@@ -547,8 +527,8 @@ int fid_scrfd_decode(fid_ctx *ctx, const float *const head_dev[9], const int32_t
     float *data = (float *)((char *)ws + off_data);
     FID_HIP(hipMemsetAsync(cand_count, 0, (size_t)B * 4, ctx->stream));
     const int total = ((in_h / 8) * (in_w / 8) + (in_h / 16) * (in_w / 16) + (in_h / 32) * (in_w / 32)) * num_anchors;
-    hipLaunchKernelGGL(decode_compact, dim3(fid::cdiv(total, 256), B), dim3(256), 0, ctx->stream, hv, in_h, in_w, num_anchors,
-                       conf_thres, 1.0f, 1, cc, cand_count, keys, data);
+    hipLaunchKernelGGL(decode_compact<PlaceUniform>, dim3(fid::cdiv(total, 256), B), dim3(256), 0, ctx->stream, hv, in_h, in_w, num_anchors,
+                       conf_thres, PlaceUniform{1.0f, 1}, cc, cand_count, keys, data);
     hipLaunchKernelGGL(rank_scatter, dim3(fid::cdiv(cc, 256), B), dim3(256), 0, ctx->stream, cand_count, keys, data, rec_dev, cc);
     FID_HIP(hipMemcpyAsync(counts_dev, cand_count, (size_t)B * 4, hipMemcpyDeviceToDevice, ctx->stream));
     FID_HIP(hipGetLastError());

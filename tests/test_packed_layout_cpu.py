@@ -138,10 +138,22 @@ def test_new_entry_points_are_declared_bound_and_built():
     assert "pack" not in re.search(r"^HANDCOUNTED = (.*)$", mk, flags=re.M).group(1)
 
 
-@pytest.mark.parametrize("src,kernels", [("pack.hip", ["face_pack"]), ("align.hip", ["align_warp", "align_warp_packed"])])
-def test_new_kernels_use_no_scratch(src, kernels, tmp_path):
+_FRAMES, _ROWS = ("BgrBatch", "RaggedBatch", "Nv12Batch"), ("SlotRows", "PackedRows")
+# (source, kernel, the template arguments of every instantiation the library launches -- () for a plain kernel)
+KERNELS = [
+    ("pack.hip", "face_pack", [()]),
+    ("align.hip", "align_warp", [(f, r) for f in _FRAMES for r in _ROWS]),
+    ("align.hip", "letterbox_kernel", [("BgrBatch", "UniformGeom"), ("Nv12Batch", "UniformGeom"), ("RaggedBatch", "RaggedGeom"),
+                                       ("BgrBatch", "TileGeom"), ("Nv12Batch", "TileGeom")]),
+    ("postproc.hip", "decode_compact", [("PlaceUniform",), ("PlaceRagged",), ("PlaceTiled",)]),
+]
+
+
+@pytest.mark.parametrize("src,kernel,insts", KERNELS, ids=[k[1] for k in KERNELS])
+def test_new_kernels_use_no_scratch(src, kernel, insts, tmp_path):
     """a compile, not a run: the resource remarks of the device pass.  align_warp on the commit before the factoring: occupancy 8
-    waves / SIMD, no scratch -- the shared __device__ function must not cost it that."""
+    waves / SIMD, no scratch -- neither the shared __device__ function nor the kernel template over (frame batch, row addresser) may
+    cost any of its six instantiations that.  The one-pixel letterbox template and the decode template: no scratch, no spill."""
     hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.fail(f"hipcc not found ({hipcc}): the library cannot have been built either")
@@ -150,19 +162,19 @@ def test_new_kernels_use_no_scratch(src, kernels, tmp_path):
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     blocks = re.split(r"remark: Function Name: ", r.stderr)[1:]
+    names = sorted({a for inst in insts for a in inst})
     found = {}
     for blk in blocks:
         mangled = blk.split()[0]
-        for k in kernels:
-            if re.search(r"\d+" + k + r"E", mangled):
-                found[k] = blk
-    assert sorted(found) == sorted(kernels), (sorted(found), r.stderr[-500:])
+        if re.search(r"\d+" + kernel + (r"I" if names else r"E"), mangled):          # (letterbox_kernel4E is not letterbox_kernelI)
+            found[tuple(a for a in names if re.search(r"\d+" + a + r"E", mangled))] = blk
+    assert sorted(found) == sorted(tuple(sorted(i)) for i in insts), (sorted(found), r.stderr[-500:])
     for k, blk in found.items():
         assert int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", blk).group(1)) == 0, k
         assert int(re.search(r"VGPRs Spill: (\d+)", blk).group(1)) == 0, k
         # (occupancy is what "not worse than before the factoring" means for a launch; with ROCm 7.2 (AMD clang 22.0.0git, roc-7.2.0)
         # align_warp compiles to 37 VGPRs before and after -- a register count is the compiler's to move, so it is not asserted)
-        if k.startswith("align_warp"):
+        if kernel == "align_warp":
             assert int(re.search(r"Occupancy \[waves/SIMD\]: (\d+)", blk).group(1)) >= 8, k
 
 

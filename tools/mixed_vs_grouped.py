@@ -111,7 +111,7 @@ def main():
     mixed_chain(0)
     rows_m = total_rows(B)
     log(f"recogniser rows: groups {rows_g} (sum {sum(rows_g)}), mixed {rows_m}")
-    assert rows_m > 0 and all(r > 0 for r in rows_g)
+    assert rows_m > 0 and sum(rows_g) > 0                  # (a group the detector finds nothing in ends after its pack: chain())
 
     def grouped():
         for gi in range(n_sizes):
