@@ -465,6 +465,80 @@ int fid_track_coast_host(int32_t *entries, int S, int T, const int32_t *stream, 
                          const int32_t *track, const int32_t *ident_idx, const float *ident_score, const fid_coast_config *cfg,
                          float *det_out, int32_t *counts_out, int32_t *track_out, int32_t *idx_out, float *score_out);
 
+/* ---- re-linking: a returning face gets its earlier track's PERSON ID by embedding (no reference analogue: the reference re-identifies against
+ * a gallery of names only, so a stranger who walks behind a pillar for longer than max_age frames comes back as somebody new).  A relinker
+ * follows a tracker on the device: it keeps the latest embedding of every live track and, per stream, a small pool of recently ended tracks;
+ * when a new track gets its first embedding and that embedding scores above a threshold against a pooled one, the new track inherits the old
+ * track's person id.  A person id is the id of the first track of a chain; its namespace is the stream's track ids.  Streams never share
+ * anything.  It changes nothing the tracker decides; fid_track_step never sees a person id.
+ *
+ * A relinker belongs to a tracker's shape: S streams x T slots, a pool of L entries per stream (1 <= L <= FID_RELINK_MAX_POOL), embeddings of
+ * dim fp16 values, dim >= 8 and a multiple of 8.  State, all in device memory, owned by the handle:
+ *   live table, int32 [S,T,FID_RELINK_WORDS]:  0 track id (-1: empty, then every other word is 0)   1 person id   2 has_q   3 bits of the link
+ *     score (0: never linked)   4 seen, the frame number of the track's latest row   5 missed   6 the track id it was linked from (-1: none)
+ *     7 0;  plus live_q fp16 [S,T,dim].
+ *   pool, int32 [S,L,FID_RELINK_WORDS]:  0 person id (-1: free, then every other word is 0)   1 the ended track's id   2 its seen   3 .. 7  0;
+ *     plus pool_q fp16 [S,L,dim].
+ *   a frame counter per stream: the non-skipped frames since create or reset, 0-based, as the keeper's.
+ *   The q row of an empty live entry or a free pool entry is whatever it last held (zeros after create or reset).
+ * Config: thresh finite in [0, 1); window >= 0, the frames a pooled track waits; max_age >= 0, which must be the tracker's.
+ *
+ * fid_track_relink follows one completed step, i.e. a step after its fid_track_identify; its order relative to fid_track_keep and
+ * fid_track_coast is free; at most once per step (the tracker's serial decides, as for the keeper).  It takes the step's stream, B, cap,
+ * counts, track, offsets, src, row_cap, n_rows and the unit rows q_dev fp16 [n_rows,dim].  A detection is TRACKED when its word
+ * track[b,f,1] >= 0, its id t = track[b,f,0] >= 0 and its slot = word & 63 is < T.  Per stream s, over its frames b in batch order
+ * (stream[b] < 0: the frame is skipped without ageing and gets {-1,-1} everywhere), n = the stream's frame number,
+ * k_b = min(max(counts[b], 0), cap):
+ *   0. expiry.  A pool entry with n - seen > window becomes free.
+ *   1. sightings.  Tracked detections f = 0 .. k_b - 1 in order.  If the slot's live entry is empty, holds another id, or the word carries
+ *      FID_TRACK_STARTED: a non-empty old entry RETIRES, and the entry BEGINS: id = person = t, has_q = 0, link score 0, seen 0, missed 0,
+ *      linked-from -1.  The slot counts as seen in this frame and missed = 0.
+ *   2. rows.  i in [max(offsets[b], 0), min(offsets[b+1], n_rows, row_cap)) in table order, where src[i] is a tracked detection of this frame
+ *      (b * cap <= src[i] < b * cap + k_b); other rows are ignored.  The row acts on its slot's live entry.  If has_q == 0 the row is scored
+ *      against every non-free pool entry of s: the fp32 sum over dim of the fp16 products (exact in fp32; the summation order is free).  The
+ *      best is the maximum score, the lowest pool index among equals; a NaN is never best.  If best > thresh (strict): person = the entry's
+ *      person, linked-from = its track id, the link score is stored and the pool entry becomes free -- a pooled track is claimed once.  In
+ *      every case live_q = the row, has_q = 1, seen = n.
+ *   3. output, person_dev int32 [B,cap,2]: a tracked detection gets {its slot's live person, word | (FID_TRACK_RELINKED if that person differs
+ *      from the live id)}; everything else {-1,-1}.  Every byte is defined.
+ *   4. ageing, slots ascending.  A non-empty live entry that was not seen in this frame gets missed += 1; if missed > max_age it retires and
+ *      the entry becomes empty.
+ *   RETIRE: an entry with has_q == 0 just vanishes.  Otherwise it goes into the lowest free pool index; with no free index it overwrites
+ *      the entry with the smallest seen, the lowest index among equals.  It goes in as (person, id, seen, q).
+ * With the tracker's max_age, steps 1 and 4 mirror the tracker's own slot life exactly: after any step live word 0 equals
+ * fid_tracker_read's slot ids.  The result does not depend on how frames are split into calls, as long as row_cap cuts no row.
+ * fid_relinker_reset: stream >= 0 gives that stream the fresh state (empty live entries, a free pool, zero q rows, frame 0), -1 all.
+ * fid_relinker_read (synchronises; tests and debugging): live_host int32 [S,T,8], pool_host int32 [S,L,8], frames_host int32 [S] and, where
+ * not NULL, live_q_host fp16 [S,T,dim], pool_q_host fp16 [S,L,dim].
+ * FID_E_INVALID, nothing enqueued, state and outputs untouched: a NULL pointer; a shape outside the ranges above or different from the
+ * tracker's; thresh not finite or outside [0, 1); window < 0 or max_age < 0; n_rows outside [0, row_cap]; B, cap, row_cap or a stream array
+ * that differ from the tracker's last step's; a tracker that has run no step, or whose step still waits for its identify; a second relink for
+ * one step; a reset of a stream outside [-1, S).  fid_track_relink is asynchronous on the context's stream, one launch, never reads back and
+ * allocates nothing.
+ * fid_track_relink_host: the same walk in plain loops on HOST arrays, no device and no tracker involved (the five state arrays are the
+ * caller's, updated in place; a fresh state is word 0 = -1, everything else 0); it sums ascending.  It refuses what can be checked without a
+ * tracker. */
+typedef struct fid_relinker fid_relinker;
+typedef struct fid_relink_config {
+    float thresh;                  /* [0, 1) */
+    int32_t window;                /* >= 0 */
+    int32_t max_age;               /* >= 0: the tracker's */
+} fid_relink_config;
+#define FID_RELINK_WORDS 8
+#define FID_RELINK_MAX_POOL 64
+#define FID_TRACK_RELINKED (1 << 11)
+int fid_relinker_create(fid_ctx *ctx, int S, int T, int L, int dim, fid_relinker **out);
+int fid_relinker_destroy(fid_ctx *ctx, fid_relinker *relinker);
+int fid_relinker_reset(fid_ctx *ctx, fid_relinker *relinker, int stream);
+int fid_relinker_read(fid_ctx *ctx, fid_relinker *relinker, int32_t *live_host, int32_t *pool_host, int32_t *frames_host, uint16_t *live_q_host,
+                      uint16_t *pool_q_host);
+int fid_track_relink(fid_ctx *ctx, fid_relinker *relinker, fid_tracker *trk, const int32_t *stream, int B, int cap, const int32_t *counts_dev,
+                     const int32_t *track_dev, const int32_t *offsets_dev, const int32_t *src_dev, int row_cap, int n_rows, const uint16_t *q_dev,
+                     const fid_relink_config *cfg, int32_t *person_dev);
+int fid_track_relink_host(int32_t *live, uint16_t *live_q, int32_t *pool, uint16_t *pool_q, int32_t *frames, int S, int T, int L, int dim,
+                          const int32_t *stream, int B, int cap, const int32_t *counts, const int32_t *track, const int32_t *offsets,
+                          const int32_t *src, int row_cap, int n_rows, const uint16_t *q, const fid_relink_config *cfg, int32_t *person);
+
 /* ---- drawing detections, names and scores onto the frames (reference main.py:130-148 with utils/helpers.py:126-179 draw_bbox / draw_bbox_info):
  * the overlay of a whole batch in place on the device, enqueued behind the match with nothing read back first.  OpenCV's thick-line caps and
  * Hershey font are NOT reproduced; taken from the reference are the integer truncation of the box, the corner length, the

@@ -97,6 +97,34 @@ class CoastConfig(C.Structure):
     def __init__(self, hold=5, predict=True, grow=0.05):
         super().__init__(int(hold), int(bool(predict)), float(grow), 0)
 
+
+TRACK_RELINKED = 1 << 11         # FID_TRACK_RELINKED: the detection's person id is an earlier track's, not its own track id
+RELINK_WORDS = 8                 # FID_RELINK_WORDS: live = id, person, has_q, link score, seen, missed, linked-from, 0; pool = person, id, seen, 0 x 5
+RELINK_MAX_POOL = 64             # FID_RELINK_MAX_POOL
+
+
+class RelinkConfigC(C.Structure):
+    """fid_relink_config (include/faceid.h)"""
+    _fields_ = [("thresh", C.c_float), ("window", C.c_int32), ("max_age", C.c_int32)]
+
+
+class RelinkConfig:
+    """What a relinker is built with: the cosine a new track's first embedding must exceed against a pooled, ended track to inherit its
+    person id ([0, 1)), the frames an ended track waits in the pool, and the pool's entries per stream (1 .. 64).  max_age is not here: it
+    is the tracker's (c(max_age) gives the fid_relink_config).
+    thresh defaults to the reference's grouping_threshold (0.45) and, like it, is UNCALIBRATED for this use; window and pool are
+    uncalibrated too.  They are starting points for a user's own calibration."""
+
+    def __init__(self, thresh=0.45, window=300, pool=32):
+        self.thresh, self.window, self.pool = float(thresh), int(window), int(pool)
+
+    def c(self, max_age) -> RelinkConfigC:
+        return RelinkConfigC(self.thresh, self.window, int(max_age))
+
+    def __repr__(self):
+        return f"RelinkConfig(thresh={self.thresh}, window={self.window}, pool={self.pool})"
+
+
 FID_LABEL_MAX = 32               # name bytes a label shows
 DRAW_TRACK_ID = 1                # FID_DRAW_TRACK_ID
 
@@ -308,6 +336,15 @@ SIGNATURES = {
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fid_track_coast_host": (C.c_int, [c_i32_p, C.c_int, C.c_int, c_i32_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fid_relinker_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_void_pp]),
+    "fid_relinker_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fid_relinker_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "fid_relinker_read": (C.c_int, [C.c_void_p, C.c_void_p, c_i32_p, c_i32_p, c_i32_p, C.c_void_p, C.c_void_p]),
+    "fid_track_relink": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i32_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fid_track_relink_host": (C.c_int, [c_i32_p, C.c_void_p, c_i32_p, C.c_void_p, c_i32_p, C.c_int, C.c_int, C.c_int, C.c_int, c_i32_p, C.c_int,
+                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
     "fid_face_gates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
     "fid_face_measure": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

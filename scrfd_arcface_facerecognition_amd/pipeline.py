@@ -670,11 +670,23 @@ class TrackedFacePipeline(PackedFacePipeline):
                 face, a named person stays in the clear, and the overlay shows the held box with the track's name and id.  hold > max_age
                 is a ValueError: the tracker has freed the track by then.  results() / results_tracked() are unchanged -- a coasted box is
                 not a detection --; results_coasted() lists the coasted entries.  The config's defaults are UNCALIBRATED.  None (the
-                default): nothing of this is launched or allocated."""
+                default): nothing of this is launched or allocated.
+
+    relink      a _lib.RelinkConfig: match() follows identify() with fid_track_relink on the step's unit rows (also with gallery=None): the
+                relinker keeps every live track's latest embedding and, per stream, a pool of `pool` recently ended tracks for `window`
+                frames; a new track whose first embedding scores above `thresh` against a pooled one inherits that track's PERSON ID (the
+                id of the first track of the chain).  results_persons() adds (person id, relinked) to results_tracked()'s tuples,
+                relinker_state() reads the tables, and draw() with DRAW_TRACK_ID prints the person id in place of the track id, so the
+                drawn number stays when a stranger returns.  With a coaster the extended table keeps TRACK ids: mapping held boxes to
+                persons is out of scope.  results() / results_tracked() are unchanged.  Only a track that has ENDED can be linked to: use
+                a short max_age with the relinker.  The config's defaults are UNCALIBRATED.  None (the default): nothing of this is
+                launched or allocated."""
 
     def __init__(self, ctx: Context, det: CompiledNet, rec: CompiledNet, *, batch: int, row_cap: int, streams: int = 1, max_tracks: int = 64,
                  iou: float = 0.3, max_age: int = 15, refresh: int = 16, retry: int = 1, best_shot: bool = False, finished_cap: int = 256,
-                 keep_crops: bool = True, measure_config=None, coast=None, **kw):
+                 keep_crops: bool = True, measure_config=None, coast=None, relink=None, **kw):
+        if relink is not None and not isinstance(relink, _lib.RelinkConfig):
+            raise TypeError(f"TrackedFacePipeline: relink must be a _lib.RelinkConfig or None, not {type(relink).__name__}")
         if coast is not None:
             if not isinstance(coast, _lib.CoastConfig):
                 raise TypeError(f"TrackedFacePipeline: coast must be a _lib.CoastConfig or None, not {type(coast).__name__}")
@@ -718,6 +730,13 @@ class TrackedFacePipeline(PackedFacePipeline):
             self.coast_track = ctx.empty((self.B, cap2, 2), np.int32)
             self.coast_idx = ctx.empty((self.B, cap2), np.int32)
             self.coast_score = ctx.empty((self.B, cap2), np.float32)
+        self.relink, self.relinker, self._relinked = relink, None, False
+        if relink is not None:
+            h = C.c_void_p()
+            check(ctx.lib.fid_relinker_create(ctx.handle, self.streams, self.max_tracks, relink.pool, self.emb_dim, C.byref(h)))
+            self.relinker = h
+            self.relink_cfg = relink.c(max_age)
+            self.person = ctx.empty((self.B, cap, 2), np.int32)
 
     def _pack(self):
         check(self.ctx.lib.fid_track_step(self.ctx.handle, self.tracker, C.c_void_p(self.post.det.ptr), C.c_void_p(self.post.counts.ptr),
@@ -725,6 +744,7 @@ class TrackedFacePipeline(PackedFacePipeline):
                                           C.c_void_p(self.track.ptr), C.c_void_p(self.offsets.ptr), C.c_void_p(self.src.ptr), self.row_cap))
         self._identified = False
         self._coasted = False                                 # (the extended tables are the previous step's until match() has run)
+        self._relinked = False
 
     def identify(self, n_rows: Optional[int] = None, idx=None, score=None):
         """fold the match of the last embed()'s rows back into the tracks (n_rows = 0: a step without a gallery or without a face)"""
@@ -749,6 +769,16 @@ class TrackedFacePipeline(PackedFacePipeline):
             self._keep(q)
         if self.coaster:
             self._coast()
+        if self.relinker:
+            self._relink(q)
+
+    def _relink(self, q=None):
+        """the step's person table: every tracked detection's person id (fid_track_relink; one launch, nothing is read back)"""
+        check(self.ctx.lib.fid_track_relink(self.ctx.handle, self.relinker, self.tracker, self._stream.ctypes.data_as(_lib.c_i32_p), self.B,
+                                            self.post.cap, C.c_void_p(self.post.counts.ptr), C.c_void_p(self.track.ptr),
+                                            C.c_void_p(self.offsets.ptr), C.c_void_p(self.src.ptr), self.row_cap, min(self.n_run, self.row_cap),
+                                            _lib._ptr(self.q if q is None else q), C.byref(self.relink_cfg), C.c_void_p(self.person.ptr)))
+        self._relinked = True
 
     def _coast(self):
         """the step's detections plus the tracks that coast, into the extended tables (fid_track_coast; nothing is read back)"""
@@ -853,6 +883,8 @@ class TrackedFacePipeline(PackedFacePipeline):
             self._identified = True
         if self.coaster:                                      # (a held box of a forgotten track would outlive it)
             check(self.ctx.lib.fid_coaster_reset(self.ctx.handle, self.coaster, int(stream)))
+        if self.relinker:                                     # (a stream's ids begin again at 0: a pooled id would name somebody else)
+            check(self.ctx.lib.fid_relinker_reset(self.ctx.handle, self.relinker, int(stream)))
 
     def tracker_state(self) -> Tuple[np.ndarray, np.ndarray]:
         """(slots int32 [streams, max_tracks, 10], per-stream int32 [streams, 2] = next id, lost) -- fid_tracker_read; synchronises"""
@@ -883,6 +915,10 @@ class TrackedFacePipeline(PackedFacePipeline):
         if self.coaster:                                      # a held box is drawn after the detections: it wins where they overlap
             return self._draw(frames_dev, H, W, labels, style, self.coast_idx, self.coast_score, self.cap2, track=self.coast_track, out=out,
                               redact=redact, det=self.coast_det, counts=self.coast_counts, cap=self.cap2)
+        if self.relinker:                                     # the person table in place of the track table: the drawn number stays
+            self._need_relinked()
+            return self._draw(frames_dev, H, W, labels, style, self.ident_idx, self.ident_score, self.post.cap, track=self.person, out=out,
+                              redact=redact)
         return self._draw(frames_dev, H, W, labels, style, self.ident_idx, self.ident_score, self.post.cap, track=self.track, out=out,
                           redact=redact)
 
@@ -909,6 +945,33 @@ class TrackedFacePipeline(PackedFacePipeline):
                               word >= 0 and bool(word & _lib.TRACK_STARTED)))
             out.append(faces)
         return out
+
+    def _need_relinked(self):
+        if self.relinker is None:
+            raise RuntimeError("TrackedFacePipeline: built without relink=RelinkConfig(...)")
+        if not self._relinked:
+            raise RuntimeError("TrackedFacePipeline: the last step has not been relinked (match() runs fid_track_relink; identify() alone does not)")
+
+    def results_persons(self, gallery: Optional[Gallery] = None):
+        """results_tracked()'s tuples plus (person id, relinked): the person id is the id of the first track of the detection's chain (the
+        track id itself for a track that was never linked, -1 for an untracked face), relinked = it is an earlier track's"""
+        self._need_relinked()
+        person = self.person.download()
+        return [[face + (int(person[b, f, 0]), person[b, f, 1] >= 0 and bool(person[b, f, 1] & _lib.TRACK_RELINKED))
+                 for f, face in enumerate(frame)] for b, frame in enumerate(self.results_tracked(gallery))]
+
+    def relinker_state(self):
+        """the relinker's tables (include/faceid.h: the words): dict of live int32 [streams, max_tracks, 8], pool int32 [streams, pool, 8],
+        frames int32 [streams], live_q fp16 [streams, max_tracks, dim], pool_q fp16 [streams, pool, dim] -- fid_relinker_read; synchronises"""
+        if self.relinker is None:
+            raise RuntimeError("TrackedFacePipeline: built without relink=RelinkConfig(...)")
+        S, T, L = self.streams, self.max_tracks, self.relink.pool
+        st = dict(live=np.empty((S, T, _lib.RELINK_WORDS), np.int32), pool=np.empty((S, L, _lib.RELINK_WORDS), np.int32),
+                  frames=np.empty(S, np.int32), live_q=np.empty((S, T, self.emb_dim), np.float16), pool_q=np.empty((S, L, self.emb_dim), np.float16))
+        check(self.ctx.lib.fid_relinker_read(self.ctx.handle, self.relinker, st["live"].ctypes.data_as(_lib.c_i32_p),
+                                             st["pool"].ctypes.data_as(_lib.c_i32_p), st["frames"].ctypes.data_as(_lib.c_i32_p),
+                                             st["live_q"].ctypes.data_as(C.c_void_p), st["pool_q"].ctypes.data_as(C.c_void_p)))
+        return st
 
     def _need_coaster(self):
         if self.coaster is None:
@@ -970,6 +1033,9 @@ class TrackedFacePipeline(PackedFacePipeline):
         return self.rec.read(self.rec.low.outputs[0], kept).reshape(kept, -1), offsets
 
     def close(self):
+        if self.relinker:
+            self.ctx.lib.fid_relinker_destroy(self.ctx.handle, self.relinker)
+            self.relinker = None
         if self.coaster:
             self.ctx.lib.fid_coaster_destroy(self.ctx.handle, self.coaster)
             self.coaster = None

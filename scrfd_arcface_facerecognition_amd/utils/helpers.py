@@ -174,6 +174,58 @@ def coast_tracks(entries, stream, det, counts, track, ident_idx=None, ident_scor
     return outs
 
 
+# ---- re-linking a returning face to its earlier track (no reference analogue: the reference re-identifies against a gallery only) ----
+def relink_tracks(state, stream, counts, track, offsets, src, q, n_rows=None, config=None, max_age=15):
+    """fid_track_relink_host on numpy arrays, no device: state = dict(live int32 [S,T,8], pool int32 [S,L,8], frames int32 [S],
+    live_q fp16 [S,T,dim], pool_q fp16 [S,L,dim]), updated in place (relink_state() makes a fresh one); the step's stream [B], counts [B],
+    track [B,cap,2], offsets [B+1], src [row_cap] and the unit fp16 rows q [>= n_rows, dim] (n_rows: default len(q)); config:
+    _lib.RelinkConfig (default: its UNCALIBRATED defaults; its pool must be the state's); max_age: the tracker's.
+    -> person int32 [B,cap,2] = {person id, word | TRACK_RELINKED}."""
+    from .._lib import RELINK_WORDS, RelinkConfig, load
+    live, pool, frames, live_q, pool_q = (state[k] for k in ("live", "pool", "frames", "live_q", "pool_q"))
+    for a, dt, nd in ((live, np.int32, 3), (pool, np.int32, 3), (frames, np.int32, 1), (live_q, np.float16, 3), (pool_q, np.float16, 3)):
+        if not (isinstance(a, np.ndarray) and a.dtype == dt and a.ndim == nd and a.flags.c_contiguous):
+            raise ValueError("relink_tracks needs the contiguous state arrays of relink_state()")
+    S, T = live.shape[:2]
+    L, dim = pool.shape[1], live_q.shape[2]
+    if live.shape[2] != RELINK_WORDS or pool.shape != (S, L, RELINK_WORDS) or frames.shape != (S,) or live_q.shape != (S, T, dim) or \
+            pool_q.shape != (S, L, dim):
+        raise ValueError("relink_tracks: the state arrays do not belong together")
+    cfg = config if config is not None else RelinkConfig(pool=L)
+    if cfg.pool != L:
+        raise ValueError(f"relink_tracks: config.pool = {cfg.pool}, the state's pool has {L} entries")
+    track = np.ascontiguousarray(track, dtype=np.int32)
+    if track.ndim != 3 or track.shape[2] != 2:
+        raise ValueError(f"relink_tracks needs track [B,cap,2], not {track.shape}")
+    B, cap = track.shape[:2]
+    stream = np.ascontiguousarray(stream, dtype=np.int32).reshape(B)
+    counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(B)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int32).reshape(B + 1)
+    src = np.ascontiguousarray(src, dtype=np.int32).reshape(-1)
+    q = np.ascontiguousarray(q, dtype=np.float16).reshape(-1, dim)
+    n = len(q) if n_rows is None else int(n_rows)
+    if n > len(q):
+        raise ValueError(f"relink_tracks: n_rows = {n}, q has {len(q)} rows")
+    person = np.empty((B, cap, 2), np.int32)
+    c = cfg.c(max_age)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    check(load().fid_track_relink_host(i32(live), p(live_q), i32(pool), p(pool_q), i32(frames), S, T, L, dim, i32(stream), B, cap, p(counts),
+                                       p(track), p(offsets), p(src), len(src), n, p(q), C.byref(c), p(person)))
+    return person
+
+
+def relink_state(streams, max_tracks, pool, dim):
+    """a fresh relinker state for relink_tracks: every live entry empty, every pool entry free"""
+    from .._lib import RELINK_WORDS
+    st = dict(live=np.zeros((streams, max_tracks, RELINK_WORDS), np.int32), pool=np.zeros((streams, pool, RELINK_WORDS), np.int32),
+              frames=np.zeros(streams, np.int32), live_q=np.zeros((streams, max_tracks, dim), np.float16),
+              pool_q=np.zeros((streams, pool, dim), np.float16))
+    st["live"][..., 0] = -1
+    st["pool"][..., 0] = -1
+    return st
+
+
 # ---- density clusters of embeddings (no reference analogue: its clustering_results/ come from the greedy visit loop) ----
 def cluster_embeddings(embeddings, threshold: float = 0.45, min_samples: int = 2):
     """fid_cluster_host on numpy arrays, no device: embeddings [n, dim] (any scale; a zero row takes no part) are normalised in float64 and
