@@ -1041,6 +1041,48 @@ int fid_gallery_cluster(fid_ctx *ctx, fid_gallery *g, const int32_t *rows_dev, i
                         int32_t *degree_dev, int32_t *via_dev, float *score_dev, int32_t *summary_dev);
 int fid_cluster_host(const void *rows_f16, int G, int dim, const int32_t *rows, int n, float thresh, int min_pts, int32_t *label,
                      int32_t *degree, int32_t *via, float *score, int32_t *summary);
+/* Genuine / impostor score distributions of LABELLED stored faces: what the thresholds of this library are calibrated with.  Over all pairs of
+ * labelled faces, how are same-person and different-person cosines distributed, which threshold gives a wanted false-accept rate, and which
+ * stored faces are probably mislabelled -- as ONE asynchronous call.  No reference analogue: its thresholds are constants of config.json.
+ * rows_dev: int32 [n], the gallery row of every position k = 0 .. n - 1, exactly as in fid_gallery_cluster; NULL = positions are the gallery
+ * rows 0 .. G - 1 and n is ignored.  labels_dev: int32 [n], the person of every position; a negative label = unlabelled.
+ * A position TAKES PART when its row is inside [0, G), the row holds a non-zero element (the sign bit does not count) and its label is >= 0;
+ * any other position is in no pair.
+ * Every unordered pair i < j of positions that take part is counted once.  s = the fp32 cosine of the two stored fp16 rows, from the same tile
+ * arithmetic and therefore the same sums as fid_gallery_cluster.  The pair is GENUINE when the two labels are equal, IMPOSTOR otherwise.
+ *   bin:  a non-finite s goes into no bin and is counted in summary[3].  Otherwise b = (int)floorf(s * (float)(bins / 2)) + bins / 2, clamped
+ *         to [0, bins - 1]: ONE rounded fp32 multiply.  bins is even, 2 .. FID_HIST_MAX_BINS.  With bins a power of two the multiply is exact:
+ *         bin b holds exactly the scores with -1 + 2 b / bins <= s < -1 + 2 (b + 1) / bins, and s = 1 lands in the last bin.  So for a
+ *         power-of-two bins the cumulative count from bin b upward is EXACTLY the number of pairs that `s >= thresh` accepts at
+ *         thresh = -1 + 2 b / bins -- for a thresh > 0 that is the hit rule of fid_gallery_range / fid_gallery_cluster.  For any other even
+ *         bins an edge is exact only up to the rounding of that one multiply.
+ *   hardest pairs, per position (what finds label errors in an enrolment set):
+ *         imp_via[k] = the position j != k of ANOTHER label with the HIGHEST finite score, gen_via[k] = the position j != k of the SAME label
+ *         with the LOWEST finite score; among equal scores the lowest position.  imp_score[k] / gen_score[k] = that score.  -1 and 0.0f where
+ *         there is no such pair or the position takes no part.  Scores are ordered by their order-preserving bit pattern (csrc/calib_core.h):
+ *         the order of the numbers, with -0.0 BELOW +0.0.  Every sum starts from +0.0, so a -0.0 score does not arise; the rule only pins
+ *         the corner (tests/calib_oracle.py orders the same way).
+ * Outputs (device): hist_dev uint64 [2][bins], genuine first, then impostor; imp_via_dev, gen_via_dev int32 [n]; imp_score_dev, gen_score_dev
+ * float [n]; summary_dev uint64 [4] = {positions that took part, genuine pairs, impostor pairs, non-finite pairs} (the pair totals are the
+ * sums of the two histograms).  hist_dev and summary_dev must be 8-byte aligned.  Integer sums only: the answer is the same bytes on every run.
+ * FID_E_INVALID, nothing enqueued, outputs untouched: a NULL context, gallery, labels or output pointer (or a misaligned one), n <= 0 or
+ * n > FID_HIST_MAX_ROWS, bins odd or outside 2 .. FID_HIST_MAX_BINS, dim % 32 != 0, a gallery beyond what a buffer descriptor addresses
+ * (4 GiB, as fid_gallery_cluster).
+ * Asynchronous on the context's stream; no host synchronisation beyond the scratch-arena rule of fid_match (see fid_gallery_group).  The
+ * gallery is never written.  Scratch: 16 bytes per position: no n x n matrix, no pair list.  FID_HIST_PEEL (0, the default, or 4: rounds of in-wave
+ * aggregation before the LDS counters) and FID_HIST_GRID (workgroups of the pass) in the environment are read per call, for measurements;
+ * the answer depends on neither.
+ * fid_score_hist_host: the same rule in plain loops on HOST arrays (csrc/calib_core.h), no device involved: rows_f16 [G, dim] fp16 rows in
+ * place of the gallery (any dim >= 1), rows int32 [n] or NULL, labels int32 [n], outputs as above.  Its cosine is the fp32 sum in ascending
+ * column order starting from +0.0f; the device sums in the order of its tiles.  Where the sums are exact the two are equal to the bit;
+ * elsewhere a score within summation-order rounding of a bin edge may fall on either side. */
+#define FID_HIST_MAX_ROWS (1 << 20)
+#define FID_HIST_MAX_BINS 4096
+int fid_gallery_score_hist(fid_ctx *ctx, fid_gallery *g, const int32_t *rows_dev, const int32_t *labels_dev, int n, int bins,
+                           uint64_t *hist_dev, int32_t *imp_via_dev, float *imp_score_dev, int32_t *gen_via_dev, float *gen_score_dev,
+                           uint64_t *summary_dev);
+int fid_score_hist_host(const void *rows_f16, int G, int dim, const int32_t *rows, const int32_t *labels, int n, int bins,
+                        uint64_t *hist, int32_t *imp_via, float *imp_score, int32_t *gen_via, float *gen_score, uint64_t *summary);
 /* Gallery sharded over ranks by contiguous row blocks (the 1 M-entry variant of main.py:136-142):
  * fid_match_keys scans THIS rank's rows (global index of its row 0 = first_row) for all n queries and writes one
  * packed key per query, (order-preserving bits of the score << 32) | ~global_index; after the ranks' key arrays

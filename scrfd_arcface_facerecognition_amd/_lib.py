@@ -113,7 +113,8 @@ class RelinkConfig:
     person id ([0, 1)), the frames an ended track waits in the pool, and the pool's entries per stream (1 .. 64).  max_age is not here: it
     is the tracker's (c(max_age) gives the fid_relink_config).
     thresh defaults to the reference's grouping_threshold (0.45) and, like it, is UNCALIBRATED for this use; window and pool are
-    uncalibrated too.  They are starting points for a user's own calibration."""
+    uncalibrated too.  They are starting points for a user's own calibration (engine.VectorGallery.score_distribution measures the score
+    distributions of a labelled store)."""
 
     def __init__(self, thresh=0.45, window=300, pool=32):
         self.thresh, self.window, self.pool = float(thresh), int(window), int(pool)
@@ -385,6 +386,10 @@ SIGNATURES = {
                                       C.c_void_p]),
     "fid_cluster_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
+    "fid_gallery_score_hist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fid_score_hist_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "fid_pair_verify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "fid_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),

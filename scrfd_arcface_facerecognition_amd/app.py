@@ -237,7 +237,7 @@ class FaceAnalysis:
         """Which faces of these images are the same person: get_batch(images, max_num), every face's embedding into a temporary VectorGallery
         under the id (image index, face index), then VectorGallery.cluster.  Host glue only.  -> engine.ClusterResult keyed by those pairs;
         the answer does not depend on the order of the images beyond the names of the labels.  The default threshold is the reference's
-        `grouping_threshold`; it is UNCALIBRATED for clustering."""
+        `grouping_threshold`; it is UNCALIBRATED for clustering (calibrate_faces / VectorGallery.score_distribution measure labelled faces)."""
         from .engine import VectorGallery
         faces = self.get_batch(images, max_num)
         ids = [(b, i) for b, fs in enumerate(faces) for i in range(len(fs))]
@@ -246,6 +246,24 @@ class FaceAnalysis:
             if ids:
                 store.upsert(ids, np.stack([faces[b][i]["embedding"] for b, i in ids]))
             return store.cluster(similarity_threshold, min_samples)
+        finally:
+            store._gal.close()
+
+    def calibrate_faces(self, images, labels, bins: int = 512):
+        """The genuine / impostor score distributions of a labelled set of images: get_batch(images, max_num=1), the one face of image b into a
+        temporary VectorGallery under the id b with the person labels[b] (None = unlabelled), then VectorGallery.score_distribution.  Host
+        glue only.  An image without a face is in no pair: its index is not among the ids of the result.  -> engine.ScoreDistribution keyed
+        by image index."""
+        from .engine import VectorGallery
+        if len(labels) != len(images):
+            raise ValueError(f"calibrate_faces: {len(labels)} labels for {len(images)} images")
+        faces = self.get_batch(images, max_num=1)
+        ids = [b for b, fs in enumerate(faces) if len(fs)]
+        store = VectorGallery(self.ctx, 512, capacity=max(128, len(ids)))
+        try:
+            if ids:
+                store.upsert(ids, np.stack([faces[b][0]["embedding"] for b in ids]))
+            return store.score_distribution({b: labels[b] for b in ids}, bins)
         finally:
             store._gal.close()
 

@@ -542,7 +542,8 @@ class VectorGallery:
         plus the borders that hang on them (include/faceid.h, fid_gallery_cluster, has the rule).  Positions are the ids in ascending order, as
         in find_and_merge_duplicates(via="device"), so a cluster's label is its lowest core id -- but, unlike that greedy walk, the partition
         does not depend on the order.  One upload (the rows), one call, one download (label | degree | via | score | summary as ONE buffer).
-        The default threshold is the reference's `grouping_threshold` (config.json); it is UNCALIBRATED for clustering."""
+        The default threshold is the reference's `grouping_threshold` (config.json); it is UNCALIBRATED for clustering (score_distribution
+        measures a labelled store)."""
         order = sorted(self.row_of if ids is None else ids)
         n = len(order)
         if n == 0:
@@ -557,6 +558,36 @@ class VectorGallery:
                                           C.c_void_p(out.ptr + 12 * n), C.c_void_p(out.ptr + 16 * n)))
         got = out.download()
         return cluster_result(order, got[:n], got[n:2 * n], got[2 * n:3 * n], got[3 * n:4 * n].view(np.float32), got[4 * n:])
+
+    # ---- score distributions (fid_gallery_score_hist): what a threshold is calibrated with -----------------------------------------------------------
+    def score_distribution(self, labels, bins: int = 512, ids=None) -> "ScoreDistribution":
+        """The genuine / impostor score distributions of the stored embeddings `ids` (default: all) under `labels`, a mapping id -> person (any
+        hashable; a missing id or None = unlabelled, in no pair): every pair of labelled embeddings is counted once, under "same person" or
+        "different persons", at the bin of its cosine (include/faceid.h, fid_gallery_score_hist, has the rule), and every embedding gets its
+        hardest impostor and its weakest genuine partner.  Positions are the ids in ascending order, as in cluster.  One upload (rows | labels),
+        one call, one download (hist | summary | imp_via | imp_score | gen_via | gen_score as ONE buffer).  With a power-of-two `bins` the
+        count from an edge upward is exactly what `>= threshold` accepts there."""
+        order = sorted(self.row_of if ids is None else ids)
+        n, bins = len(order), int(bins)
+        if bins < 2 or bins > HIST_MAX_BINS or bins % 2:
+            raise ValueError(f"score_distribution: bins = {bins} must be even, 2 .. {HIST_MAX_BINS}")
+        if n == 0:
+            return ScoreDistribution([], np.zeros((2, bins), np.uint64), np.zeros(0, np.int32), np.zeros(0, np.float32), np.zeros(0, np.int32),
+                                     np.zeros(0, np.float32), np.zeros(4, np.uint64))
+        if n > HIST_MAX_ROWS:
+            raise ValueError(f"score_distribution: {n} embeddings exceed the {HIST_MAX_ROWS} of one fid_gallery_score_hist call")
+        ctx = self.ctx
+        rows = np.asarray([self.row_of[i] for i in order], dtype=np.int32)
+        both = ctx.to_device(np.concatenate([rows, label_codes(order, labels)]))
+        words = 4 * bins + 8                                                          # hist and summary are uint64: they lead the buffer
+        out = ctx.empty((words + 4 * n,), np.int32)
+        at = lambda k: C.c_void_p(out.ptr + 4 * (words + k * n))
+        check(ctx.lib.fid_gallery_score_hist(ctx.handle, self._gal.handle, C.c_void_p(both.ptr), C.c_void_p(both.ptr + 4 * n), n, bins,
+                                             C.c_void_p(out.ptr), at(0), at(1), at(2), at(3), C.c_void_p(out.ptr + 16 * bins)))
+        got = out.download()
+        tail = got[words:]
+        return ScoreDistribution(order, got[:4 * bins].view(np.uint64).reshape(2, bins), tail[:n], tail[n:2 * n].view(np.float32), tail[2 * n:3 * n],
+                                 tail[3 * n:].view(np.float32), got[4 * bins:words].view(np.uint64))
 
     # ---- the visit loop (fid_gallery_group): a batch of visits grouped into persons in visit order, one call, one download ------------------------
     def _next_ids(self):
@@ -844,6 +875,107 @@ def cluster_result(ids, label, degree, via, score, summary) -> ClusterResult:
     if len(summary) > 5 and int(summary[5]) != 0:
         raise RuntimeError("fid_gallery_cluster: a union-find loop reached its bound; the labels are not to be trusted")
     return ClusterResult(ids, label, degree, via, score, summary)
+
+
+HIST_MAX_ROWS = 1 << 20                                                           # FID_HIST_MAX_ROWS
+HIST_MAX_BINS = 4096                                                              # FID_HIST_MAX_BINS
+
+
+def label_codes(ids, labels) -> np.ndarray:
+    """labels: a mapping id -> person (any hashable; a missing id or None = unlabelled) -> int32 [len(ids)]: the persons numbered in the order of
+    their first appearance, -1 = unlabelled"""
+    code: Dict[object, int] = {}
+    out = np.full(len(ids), -1, np.int32)
+    for k, i in enumerate(ids):
+        person = labels.get(i)
+        if person is not None:
+            out[k] = code.setdefault(person, len(code))
+    return out
+
+
+class ScoreDistribution:
+    """What fid_gallery_score_hist / fid_score_hist_host answer, keyed by the caller's ids (ids[k] is the id at position k):
+    genuine, impostor  uint64 [bins]: the pairs of the same / of different persons per score bin
+    edges              float64 [bins + 1]: bin b holds edges[b] <= score < edges[b + 1] (the last bin also holds score = 1; exact for a
+                       power-of-two bins, see include/faceid.h)
+    genuine_pairs, impostor_pairs, non_finite, took_part
+    and the raw per-position arrays imp_via_pos / imp_score_pos / gen_via_pos / gen_score_pos.
+    Every rate is taken at an EDGE, from the exact integer cumulative sums, with one division at the end: far(t) = the impostor pairs at or
+    above the edge / all impostor pairs, frr(t) = the genuine pairs below the edge / all genuine pairs.  At the last edge (1.0) nothing is
+    accepted.  An empty class makes its rates nan."""
+
+    def __init__(self, ids, hist, imp_via, imp_score, gen_via, gen_score, summary):
+        self.ids = list(ids)
+        hist = np.array(hist, np.uint64).reshape(2, -1)
+        self.genuine, self.impostor = hist[0].copy(), hist[1].copy()
+        self.bins = int(hist.shape[1])
+        self.edges = -1.0 + 2.0 * np.arange(self.bins + 1, dtype=np.float64) / self.bins
+        self.imp_via_pos, self.gen_via_pos = np.array(imp_via, np.int32), np.array(gen_via, np.int32)
+        self.imp_score_pos, self.gen_score_pos = np.array(imp_score, np.float32), np.array(gen_score, np.float32)
+        self.summary = np.array(summary, np.uint64)
+        self.took_part, self.genuine_pairs, self.impostor_pairs, self.non_finite = (int(v) for v in self.summary[:4])
+
+    @functools.cached_property
+    def _accepted(self):
+        """per class, the pairs at or above every edge as Python ints [bins + 1] (the last edge accepts nothing)"""
+        out = []
+        for h in (self.genuine, self.impostor):
+            acc, run = [0], 0
+            for v in h[::-1].tolist():
+                run += int(v)
+                acc.append(run)
+            out.append(acc[::-1])
+        return out
+
+    def _edge(self, threshold) -> int:
+        """the edge at or above the argument (the last one for an argument above it)"""
+        return min(int(np.searchsorted(self.edges, float(threshold), side="left")), self.bins)
+
+    def _rates(self, e: int):
+        g, i = self.genuine_pairs, self.impostor_pairs
+        far = self._accepted[1][e] / i if i else float("nan")
+        frr = (g - self._accepted[0][e]) / g if g else float("nan")
+        return far, frr
+
+    def far(self, threshold) -> float:
+        return self._rates(self._edge(threshold))[0]
+
+    def frr(self, threshold) -> float:
+        return self._rates(self._edge(threshold))[1]
+
+    def threshold_at_far(self, target: float):
+        """-> (threshold, far, frr) at the LOWEST edge whose FAR <= target; (nan, nan, nan) without impostor pairs or for a target < 0"""
+        if self.impostor_pairs:
+            for e in range(self.bins + 1):                                            # (far does not rise with the edge)
+                far, frr = self._rates(e)
+                if far <= target:
+                    return float(self.edges[e]), far, frr
+        return float("nan"), float("nan"), float("nan")
+
+    def eer(self):
+        """-> (threshold, far, frr) at the edge that minimises |far - frr|, the lowest edge among equals (compared as exact integers);
+        (nan, nan, nan) when a class is empty"""
+        g, i = self.genuine_pairs, self.impostor_pairs
+        if not g or not i:
+            return float("nan"), float("nan"), float("nan")
+        gap = [abs(self._accepted[1][e] * g - (g - self._accepted[0][e]) * i) for e in range(self.bins + 1)]
+        e = gap.index(min(gap))
+        return (float(self.edges[e]),) + self._rates(e)
+
+    def _ranked(self, via, score, k, sign):
+        pos = np.nonzero(via >= 0)[0]
+        pos = pos[np.lexsort((pos, sign * score[pos].astype(np.float64)))][:max(int(k), 0)]        # ties: the lower position = the lower id
+        return [(self.ids[p], self.ids[int(via[p])], float(score[p])) for p in pos.tolist()]
+
+    def hardest_impostors(self, k: int = 10):
+        """the k ids with the highest score against an id of ANOTHER person: [(id, other id, score)], score-descending -- two photographs of one
+        person under two labels show up here"""
+        return self._ranked(self.imp_via_pos, self.imp_score_pos, k, -1.0)
+
+    def weakest_genuines(self, k: int = 10):
+        """the k ids with the lowest score against an id of the SAME person: [(id, other id, score)], score-ascending -- a stranger filed under a
+        person's label shows up here"""
+        return self._ranked(self.gen_via_pos, self.gen_score_pos, k, 1.0)
 
 
 def _gallery_ptr(gal: Gallery) -> int:

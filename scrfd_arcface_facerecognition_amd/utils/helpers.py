@@ -232,7 +232,8 @@ def cluster_embeddings(embeddings, threshold: float = 0.45, min_samples: int = 2
     rounded to fp16 as the gallery stores them, then clustered by the rule of fid_gallery_cluster (include/faceid.h): two rows hit at a cosine
     >= threshold (and > 0), a row with `min_samples` rows within the threshold, itself counted, is a core, clusters are connected cores plus
     their borders, labelled by their lowest core.  The answer does not depend on the order of the rows.  The default threshold is the
-    reference's `grouping_threshold`; it is UNCALIBRATED for clustering.  -> engine.ClusterResult keyed by the row index."""
+    reference's `grouping_threshold`; it is UNCALIBRATED for clustering (score_distribution below measures labelled rows).  -> engine.ClusterResult
+    keyed by the row index."""
     from .._lib import load
     from ..engine import cluster_result
     x = np.asarray(embeddings, dtype=np.float64)
@@ -247,6 +248,37 @@ def cluster_embeddings(embeddings, threshold: float = 0.45, min_samples: int = 2
     p = lambda a: a.ctypes.data_as(C.c_void_p)
     check(load().fid_cluster_host(p(unit), n, dim, None, n, C.c_float(threshold), int(min_samples), p(label), p(degree), p(via), p(score), p(summary)))
     return cluster_result(list(range(n)), label, degree, via, score, summary)
+
+
+# ---- genuine / impostor score distributions of labelled embeddings (no reference analogue: its thresholds are constants of config.json) ----
+def score_distribution(embeddings, labels, bins: int = 512):
+    """fid_score_hist_host on numpy arrays, no device: embeddings [n, dim] (any scale; a zero row takes no part) are normalised in float64 and
+    rounded to fp16 as the gallery stores them (as cluster_embeddings does); labels: the person of every row, a sequence of n hashables (None =
+    unlabelled) or a mapping row index -> person.  Every pair of labelled rows is counted once into the genuine or the impostor histogram by the
+    rule of fid_gallery_score_hist (include/faceid.h).  -> engine.ScoreDistribution keyed by the row index."""
+    from .._lib import load
+    from ..engine import HIST_MAX_BINS, ScoreDistribution, label_codes
+    x = np.asarray(embeddings, dtype=np.float64)
+    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"score_distribution needs embeddings [n, dim], not {x.shape}")
+    n, dim = x.shape
+    bins = int(bins)
+    if bins < 2 or bins > HIST_MAX_BINS or bins % 2:
+        raise ValueError(f"score_distribution: bins = {bins} must be even, 2 .. {HIST_MAX_BINS}")
+    if not hasattr(labels, "get"):
+        if len(labels) != n:
+            raise ValueError(f"score_distribution: {len(labels)} labels for {n} rows")
+        labels = dict(enumerate(labels))
+    codes = label_codes(range(n), labels)
+    nrm = np.sqrt((x * x).sum(1, keepdims=True))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        unit = np.ascontiguousarray(np.where(nrm > 0, x / np.where(nrm > 0, nrm, 1), 0).astype(np.float16))
+    hist, summary = np.empty((2, bins), np.uint64), np.empty(4, np.uint64)
+    imp_via, gen_via = np.empty(n, np.int32), np.empty(n, np.int32)
+    imp_score, gen_score = np.empty(n, np.float32), np.empty(n, np.float32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    check(load().fid_score_hist_host(p(unit), n, dim, None, p(codes), n, bins, p(hist), p(imp_via), p(imp_score), p(gen_via), p(gen_score), p(summary)))
+    return ScoreDistribution(list(range(n)), hist, imp_via, imp_score, gen_via, gen_score, summary)
 
 
 # ---- drawing (reference utils/helpers.py:126-179): with OpenCV on the host, cv2's primitives; without it, the library's host rasteriser
