@@ -1083,6 +1083,67 @@ int fid_gallery_score_hist(fid_ctx *ctx, fid_gallery *g, const int32_t *rows_dev
                            uint64_t *summary_dev);
 int fid_score_hist_host(const void *rows_f16, int G, int dim, const int32_t *rows, const int32_t *labels, int n, int bins,
                         uint64_t *hist, int32_t *imp_via, float *imp_score, int32_t *gen_via, float *gen_score, uint64_t *summary);
+/* Identity templates: ONE gallery row per person from MANY stored faces -- the weighted mean of the person's stored rows, re-normalised, with
+ * the faces that disagree with the mean left out -- as ONE asynchronous call.  No reference analogue: its build_targets takes one photograph per
+ * name.  The sums are taken EXACTLY, in integers, so the answer is the same bytes whatever the order of the positions, the launch geometry or
+ * the arrival order of an atomic: device, host twin and tests/template_oracle.py agree byte for byte on ANY input.
+ * Positions: rows_dev int32 [n], the gallery row of every position k = 0 .. n - 1, exactly as in fid_gallery_cluster / fid_gallery_score_hist;
+ * NULL = positions are the gallery rows 0 .. G - 1 and n is ignored.  A row may occur at several positions.  labels_dev int32 [n]: the person
+ * of position k.  weights_dev int32 [n]: an integer weight; NULL = every weight is 1.
+ * A position TAKES PART (is a MEMBER of person labels[k]) when its row is inside [0, G), 0 <= label < P, 1 <= weight <= 255, the row holds a
+ * non-zero element (the sign bit does not count) and every element of the row is finite with |x| <= 2 (stored rows are unit rows: the element
+ * condition only pins corners).  A position whose row, label and weight are in range but whose elements fail is counted in summary[4].  No
+ * other position takes part in any sum.
+ *   sum:      an fp16 number with |x| <= 2 is an integer multiple of 2^-24: X_kc = x_kc * 2^24 is an exact integer with |X| <= 2^25.
+ *             S_pc = sum of w_k * X_kc over the members of p, in int64.  With n <= FID_TEMPLATE_MAX_ROWS = 2^20 and w <= 255:
+ *             |S| <= 2^20 * 255 * 2^25 < 2^53, so the sum cannot overflow and its conversion to double is exact.
+ *   norm:     the only floating-point reduction of the call, so its order is part of the ABI.  q_c = (double)S_c * (double)S_c, rounded.
+ *             Lane l of 64 owns the columns c with (c / 8) % 64 == l -- eight consecutive columns of every block of 512, what a 16-byte load
+ *             per lane brings -- and adds its q_c in ascending c, starting from +0.0 (columns at or beyond dim contribute nothing).  Six
+ *             butterfly rounds follow, lane l adding lane l ^ o for o = 32, 16, 8, 4, 2, 1, then sqrt.  Every operation is a separately
+ *             rounded IEEE fp64 operation, no FMA contraction.  (numpy: q padded to a multiple of 512, reshape(-1, 64, 8), a sequential add
+ *             over the first and then the last axis index, six folds.)
+ *   template: t_c = (double)S_c / nrm in fp64, rounded to fp32, then rounded to fp16, both to nearest even (numpy:
+ *             .astype(float32).astype(float16)).  If S is the zero vector (no member, or members that cancel) the template is the all-zero
+ *             row, which every search of this library treats as empty.
+ *   trimming: one round.  T_c = the fp16 template as an integer, as above; D_k = sum over c of X_kc * T_c in int64 (|D| <= 2^49 * dim);
+ *             score[k] = (float)((double)D_k * 2^-48), each conversion rounded to nearest once.  A member is KEPT when score[k] >= min_score,
+ *             compared in fp32; min_score <= -2 keeps every member (the scores are still reported).  The final template of a person is the
+ *             rule above on its kept members only; with nothing dropped it is the first one.  A person whose members are all dropped gets
+ *             the zero row.  The reported score is the one the decision used: against the FIRST template.
+ * Outputs (device): templates_f16_dev fp16 [P, dim] (16-byte aligned); score_dev float [n] (0.0f for a position that takes no part); kept_dev
+ * int32 [n]: 1 kept, 0 dropped, -1 takes no part; person_dev int32 [P, 4] = {members, kept members, position of the lowest-scoring member,
+ * position of the highest-scoring member} (the lowest position among equal scores; -1 where there is no member); cohesion_dev float [P] =
+ * (float)(nrm_final / ((double)W_kept * 16777216.0)), W_kept the weights of the kept members: the resultant length of the weighted mean,
+ * in [0, 1] for unit rows, 1 when all kept faces are the same vector, 0.0f for a zero template; summary_dev int64 [6] (8-byte aligned) =
+ * {positions that took part, persons with >= 1 member, persons (of all P) with a zero template, positions dropped, positions rejected for their
+ * elements, 0}.
+ * FID_E_INVALID, nothing enqueued, outputs untouched: a NULL context, gallery, labels or output pointer, a misaligned summary_dev or
+ * templates_f16_dev, n <= 0 or n > FID_TEMPLATE_MAX_ROWS, P <= 0 or P > n, a non-finite min_score, dim % 32 != 0 or
+ * dim > FID_TEMPLATE_MAX_DIM, a gallery beyond 4 GiB (as fid_gallery_score_hist).
+ * Asynchronous on the context's stream; no host synchronisation beyond the scratch-arena rule of fid_match (see fid_gallery_group).  The
+ * gallery is never written.  Scratch: 12 bytes per position, 48 per person, and one accumulator row of int64 per person with more than
+ * FID_TEMPLATE_CHUNK members (room for n / (FID_TEMPLATE_CHUNK + 1) rows): no [P, dim] array of sums.  A wave sums up to FID_TEMPLATE_CHUNK
+ * members; a person with more is split, and its chunks combine through 64-bit integer atomic adds.  FID_TEMPLATE_CHUNK (16 .. 65536) in the
+ * environment overrides the chunk per call, and FID_TEMPLATE_COMBINE=pass replaces the atomics by partial rows (one per chunk of a split person, at
+ * most 2 n / chunk + 1) and a second pass that adds them up, both for measurements; the answer depends on neither.
+ * fid_templates_host: the same rule in plain loops on HOST arrays (csrc/template_core.h), no device involved: rows_f16 [G, dim] fp16 rows in
+ * place of the gallery (any dim 1 .. FID_TEMPLATE_MAX_DIM), rows / weights int32 [n] or NULL, outputs as above, equal to the device's byte
+ * for byte.
+ * fid_gallery_put_rows_f16: gallery row rows_dev[i] = the fp16 row i of src_f16_dev [n, dim] (device memory, 16-byte aligned), byte for byte:
+ * no re-normalisation, where fid_gallery_set_rows takes host fp32 and rounds again.  How templates enter a gallery where they lie.  The rows
+ * are checked on the host first (one small download, so the call waits for the work enqueued before it): a row outside [0, G) refuses the
+ * whole call with FID_E_INVALID and nothing is written.  Rows should be distinct (which source wins otherwise is unspecified).  Like
+ * fid_gallery_group it does not refresh the int8 copy of fid_gallery_quantize: quantise again before the next coarse search. */
+#define FID_TEMPLATE_MAX_ROWS (1 << 20)
+#define FID_TEMPLATE_MAX_DIM 4096
+#define FID_TEMPLATE_CHUNK 256
+int fid_gallery_templates(fid_ctx *ctx, fid_gallery *g, const int32_t *rows_dev, const int32_t *labels_dev, const int32_t *weights_dev, int n,
+                          int P, float min_score, void *templates_f16_dev, float *score_dev, int32_t *kept_dev, int32_t *person_dev,
+                          float *cohesion_dev, int64_t *summary_dev);
+int fid_templates_host(const void *rows_f16, int G, int dim, const int32_t *rows, const int32_t *labels, const int32_t *weights, int n, int P,
+                       float min_score, void *templates_f16, float *score, int32_t *kept, int32_t *person, float *cohesion, int64_t *summary);
+int fid_gallery_put_rows_f16(fid_ctx *ctx, fid_gallery *g, const int32_t *rows_dev, const void *src_f16_dev, int n);
 /* Gallery sharded over ranks by contiguous row blocks (the 1 M-entry variant of main.py:136-142):
  * fid_match_keys scans THIS rank's rows (global index of its row 0 = first_row) for all n queries and writes one
  * packed key per query, (order-preserving bits of the score << 32) | ~global_index; after the ranks' key arrays

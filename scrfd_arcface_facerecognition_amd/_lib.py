@@ -227,6 +227,8 @@ def label_arrays(names, colors=None):
         bgr = np.ascontiguousarray(np.asarray(colors).reshape(len(raw), 3), dtype=np.uint8)
     return b"".join(bytes(r) for r in raw), offsets, bgr
 
+TEMPLATE_MAX_ROWS = 1 << 20       # FID_TEMPLATE_MAX_ROWS: positions of one fid_gallery_templates call
+TEMPLATE_CHUNK = 256             # FID_TEMPLATE_CHUNK: the members one wave sums; a person with more is split over several waves
 
 SIGNATURES = {
     "fid_labels_create": (C.c_int, [C.c_void_p, C.c_char_p, c_i32_p, C.c_void_p, C.c_int, c_void_pp]),
@@ -390,6 +392,11 @@ SIGNATURES = {
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "fid_score_hist_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fid_gallery_templates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fid_templates_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fid_gallery_put_rows_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "fid_pair_verify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "fid_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),

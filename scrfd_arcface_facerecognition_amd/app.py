@@ -267,6 +267,30 @@ class FaceAnalysis:
         finally:
             store._gal.close()
 
+    def enroll_faces(self, images, labels, min_score=None, weights=None):
+        """One gallery row per person from a labelled set of images: get_batch(images, max_num=1), the one face of image b into a temporary
+        VectorGallery under the id b with the person labels[b] (None = unlabelled), then VectorGallery.enroll_templates into a NEW store keyed
+        by person.  Host glue only, shaped like calibrate_faces.  An image without a face takes no part.  weights: None, or the quality in
+        [0, 1] of every image; min_score: None (the default) drops no face -- no value has been measured, calibrate_faces is the tool to
+        choose one with.  -> (VectorGallery of the persons, engine.TemplateResult keyed by image index); the caller closes the store."""
+        from .engine import VectorGallery
+        if len(labels) != len(images) or (weights is not None and len(weights) != len(images)):
+            raise ValueError(f"enroll_faces: {len(labels)} labels / {None if weights is None else len(weights)} weights for {len(images)} images")
+        faces = self.get_batch(images, max_num=1)
+        ids = [b for b, fs in enumerate(faces) if len(fs)]
+        store = VectorGallery(self.ctx, 512, capacity=max(128, len(ids)))
+        persons = VectorGallery(self.ctx, 512, capacity=max(128, len({labels[b] for b in ids if labels[b] is not None})))
+        try:
+            if ids:
+                store.upsert(ids, np.stack([faces[b][0]["embedding"] for b in ids]))
+            res = store.enroll_templates({b: labels[b] for b in ids}, persons, None if weights is None else {b: weights[b] for b in ids}, min_score)
+        except Exception:
+            persons._gal.close()
+            raise
+        finally:
+            store._gal.close()
+        return persons, res
+
     def process_visits(self, images, store, **thresholds):
         """The reference's process_visit_data (smart_face_recognition.py:1721-2005) for a list of images (sizes may differ), one visit each, in
         order: best face and its gates per image (the batch form of best_face, :1473-1519, through get_batch), then `store.group_visits` on the

@@ -589,6 +589,75 @@ class VectorGallery:
         return ScoreDistribution(order, got[:4 * bins].view(np.uint64).reshape(2, bins), tail[:n], tail[n:2 * n].view(np.float32), tail[2 * n:3 * n],
                                  tail[3 * n:].view(np.float32), got[4 * bins:words].view(np.uint64))
 
+    # ---- identity templates (fid_gallery_templates): one row per person from many stored faces --------------------------------------------------------
+    def _templates_call(self, labels, weights, min_score, ids):
+        """-> (TemplateResult, the device buffer that holds the call's outputs or None, the byte offset of the templates in it)"""
+        order = sorted(self.row_of if ids is None else ids)
+        codes = label_codes(order, labels)
+        persons = persons_of(order, labels, codes)
+        n, P = len(order), len(persons)
+        if P == 0:
+            return TemplateResult(order, [], np.zeros((0, self.dim), np.float16), np.zeros(n, np.float32), np.full(n, -1, np.int32),
+                                  np.zeros((0, 4), np.int32), np.zeros(0, np.float32), np.zeros(6, np.int64)), None, 0
+        if n > TEMPLATE_MAX_ROWS:
+            raise ValueError(f"templates: {n} embeddings exceed the {TEMPLATE_MAX_ROWS} of one fid_gallery_templates call")
+        ctx, dim = self.ctx, self.dim
+        rows = np.asarray([self.row_of[i] for i in order], dtype=np.int32)
+        inp = ctx.to_device(np.concatenate([rows, codes, weight_codes(order, weights)]))
+        tw = P * dim // 2                                                             # int32 words of the templates
+        out = ctx.empty((12 + tw + 2 * n + 5 * P,), np.int32)                         # summary (int64 [6]) | templates | score | kept | person | cohesion
+        at = lambda w: C.c_void_p(out.ptr + 4 * w)
+        check(ctx.lib.fid_gallery_templates(ctx.handle, self._gal.handle, C.c_void_p(inp.ptr), C.c_void_p(inp.ptr + 4 * n), C.c_void_p(inp.ptr + 8 * n),
+                                            n, P, C.c_float(TEMPLATE_KEEP_ALL if min_score is None else float(min_score)), at(12), at(12 + tw),
+                                            at(12 + tw + n), at(12 + tw + 2 * n), at(12 + tw + 2 * n + 4 * P), at(0)))
+        got = out.download()
+        per = got[12 + tw:]
+        res = TemplateResult(order, persons, got[12:12 + tw].view(np.float16).reshape(P, dim), per[:n].view(np.float32), per[n:2 * n],
+                             per[2 * n:2 * n + 4 * P].reshape(P, 4), per[2 * n + 4 * P:].view(np.float32), got[:12].view(np.int64))
+        return res, out, 48
+
+    def templates(self, labels, weights=None, min_score=None, ids=None) -> "TemplateResult":
+        """One template per person from the stored embeddings `ids` (default: all) under `labels`, a mapping id -> person as in
+        score_distribution (a missing id or None = unlabelled, in no template): the weighted mean of the person's stored rows, re-normalised,
+        taken exactly in integers (include/faceid.h, fid_gallery_templates, has the rule), so the answer does not depend on the order of the
+        ids.  weights: a mapping id -> quality in [0, 1] (w = clip(rint(255 q), 1, 255) for q > 0; q <= 0, NaN or a missing id: the face takes
+        no part), None = equal weights.  min_score: a face whose score against its person's template is below it is dropped and the template
+        taken again from the rest; None (the default) drops nothing -- no value has been measured, score_distribution is the tool to choose one
+        with.  Positions are the ids in ascending order, persons are numbered in the order of their first appearance there.  One upload
+        (rows | labels | weights), one call, one download."""
+        return self._templates_call(labels, weights, min_score, ids)[0]
+
+    def enroll_templates(self, labels, into: "VectorGallery", weights=None, min_score=None, ids=None) -> "TemplateResult":
+        """templates(...), and every person with a non-zero template is stored in `into` (another VectorGallery of this context and dim) under
+        the person as id -- a new row, or the row the id already has -- through fid_gallery_put_rows_f16: the template rows go from the call's
+        output buffer into the gallery on the device, byte for byte.  A person whose template is the zero row is not enrolled (and what
+        `into` holds under that id stays).  -> the TemplateResult."""
+        if into.ctx is not self.ctx or into.dim != self.dim or into is self:
+            raise ValueError("enroll_templates: `into` must be another store of the same context and dim")
+        res, out, off = self._templates_call(labels, weights, min_score, ids)
+        live = [p for p in range(len(res.persons)) if res.cohesion[p] > 0]
+        if not live:
+            return res
+        for p in live:
+            pid = res.persons[p]
+            if pid not in into.row_of:
+                if not into._free:
+                    into._grow()
+                r = into._free.pop()
+                into.row_of[pid], into.id_of[r] = r, pid
+        ctx, lib = self.ctx, self.ctx.lib
+        rows_dev = ctx.to_device(np.asarray([into.row_of[res.persons[p]] for p in live], dtype=np.int32))
+        a = 0
+        while a < len(live):                                                          # one call per run of consecutive persons (one, unless a zero row lies between)
+            b = a + 1
+            while b < len(live) and live[b] == live[b - 1] + 1:
+                b += 1
+            check(lib.fid_gallery_put_rows_f16(ctx.handle, into._gal.handle, C.c_void_p(rows_dev.ptr + 4 * a),
+                                               C.c_void_p(out.ptr + off + live[a] * self.dim * 2), b - a))
+            a = b
+        into._quant_stale()
+        return res
+
     # ---- the visit loop (fid_gallery_group): a batch of visits grouped into persons in visit order, one call, one download ------------------------
     def _next_ids(self):
         """fresh integer ids above the largest integer id in the store"""
@@ -976,6 +1045,79 @@ class ScoreDistribution:
         """the k ids with the lowest score against an id of the SAME person: [(id, other id, score)], score-ascending -- a stranger filed under a
         person's label shows up here"""
         return self._ranked(self.gen_via_pos, self.gen_score_pos, k, 1.0)
+
+
+TEMPLATE_MAX_ROWS = _lib.TEMPLATE_MAX_ROWS                                        # FID_TEMPLATE_MAX_ROWS
+TEMPLATE_KEEP_ALL = -2.0                                                          # a min_score <= -2 keeps every member
+
+
+def persons_of(ids, labels, codes) -> list:
+    """the persons behind label_codes' numbers, in that order"""
+    persons = [None] * (int(codes.max()) + 1 if len(codes) else 0)
+    for k in np.nonzero(codes >= 0)[0].tolist():
+        persons[int(codes[k])] = labels.get(ids[k])
+    return persons
+
+
+def weight_codes(ids, weights) -> np.ndarray:
+    """weights: None (every weight 1) or a mapping id -> quality in [0, 1] -> int32 [len(ids)]: clip(rint(255 q), 1, 255) for q > 0; 0 (the
+    position takes no part) for q <= 0, NaN or a missing id"""
+    if weights is None:
+        return np.ones(len(ids), np.int32)
+    q = np.array([np.nan if weights.get(i) is None else float(weights.get(i)) for i in ids], np.float64).reshape(len(ids))
+    with np.errstate(invalid="ignore"):
+        return np.where(q > 0, np.clip(np.rint(255.0 * np.where(q > 0, q, 0)), 1, 255), 0).astype(np.int32)
+
+
+class TemplateResult:
+    """What fid_gallery_templates / fid_templates_host answer, keyed by the caller's ids (ids[k] is the id at position k) and persons:
+    persons    the persons, in the order of their numbers;  templates  float16 [P, dim], row p the template of persons[p] (all zero: none)
+    count, kept  int32 [P]: the faces that took part / that stayed;  cohesion  float32 [P]: the resultant length of the weighted mean of the
+               faces that stayed (1 = all the same vector, 0 = no template)
+    lowest, highest  per person the id of its lowest / highest scoring face (None without a face)
+    scores     {id: score against its person's first template} for the faces that took part;  dropped  [ids] below min_score
+    zero       [persons] without a template;  counts  {"took_part", "persons", "zero", "dropped", "rejected"}
+    and the raw per-position arrays score_pos / kept_pos (1 kept, 0 dropped, -1 took no part), person_pos [P, 4], summary."""
+
+    def __init__(self, ids, persons, templates, score, kept, person, cohesion, summary):
+        self.ids, self.persons = list(ids), list(persons)
+        self.templates = np.array(templates, np.float16)                                # [P, dim]
+        self.score_pos, self.kept_pos = np.array(score, np.float32), np.array(kept, np.int32)
+        self.person_pos = np.array(person, np.int32).reshape(-1, 4)
+        self.count, self.kept = self.person_pos[:, 0].copy(), self.person_pos[:, 1].copy()
+        self.cohesion, self.summary = np.array(cohesion, np.float32), np.array(summary, np.int64)
+        self.counts = dict(zip(("took_part", "persons", "zero", "dropped", "rejected"), (int(v) for v in self.summary[:5])))
+
+    def template(self, person):
+        """the template of one person as float16 [dim]"""
+        return self.templates[self.persons.index(person)]
+
+    @functools.cached_property
+    def scores(self):
+        return {self.ids[k]: float(self.score_pos[k]) for k in np.nonzero(self.kept_pos >= 0)[0].tolist()}
+
+    @functools.cached_property
+    def dropped(self):
+        return [self.ids[k] for k in np.nonzero(self.kept_pos == 0)[0].tolist()]
+
+    @functools.cached_property
+    def zero(self):
+        return [self.persons[p] for p in np.nonzero(~(self.cohesion > 0))[0].tolist()]
+
+    @functools.cached_property
+    def lowest(self):
+        return [self.ids[k] if k >= 0 else None for k in self.person_pos[:, 2].tolist()]
+
+    @functools.cached_property
+    def highest(self):
+        return [self.ids[k] if k >= 0 else None for k in self.person_pos[:, 3].tolist()]
+
+    def weakest(self, k: int = 10):
+        """the k faces with the lowest score against their person's template, over all persons: [(id, score)], score-ascending, the lower
+        position among equals -- where to look for label errors"""
+        pos = np.nonzero(self.kept_pos >= 0)[0]
+        pos = pos[np.lexsort((pos, self.score_pos[pos].astype(np.float64)))][:max(int(k), 0)]
+        return [(self.ids[p], float(self.score_pos[p])) for p in pos.tolist()]
 
 
 def _gallery_ptr(gal: Gallery) -> int:

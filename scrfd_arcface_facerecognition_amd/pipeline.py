@@ -1197,6 +1197,38 @@ def build_targets(detector, recognizer, params, *, loader=None) -> List[Tuple[np
     return build_targets_from_images(detector, recognizer, images, names, paths)
 
 
+def merge_targets(ctx: Optional[Context], targets: Sequence[Tuple[np.ndarray, str]], min_score=None) -> List[Tuple[np.ndarray, str]]:
+    """The `(embedding, name)` list of build_targets with ONE entry per distinct name, in the order of first appearance: the entries of a name
+    become its identity template (fid_gallery_templates: the mean of their unit embeddings, re-normalised; with `min_score` the entries that
+    score below it against the mean are left out -- None, the default, drops nothing).  So a folder with ann_1.jpg, ann_2.jpg serves once the
+    caller has mapped file names to persons.  ctx: the device context (a temporary VectorGallery), or None for the host twin
+    (helpers.identity_templates: the same rule without a GPU).  A name whose entries cancel or are all dropped has no template and is left
+    out with a warning.  build_targets and gallery_from_targets stay as they are."""
+    import logging
+    if not targets:
+        return []
+    emb = np.stack([np.asarray(t[0], np.float32).reshape(-1) for t in targets])
+    names = [t[1] for t in targets]
+    if ctx is None:
+        from .utils.helpers import identity_templates
+        res = identity_templates(emb, names, None, min_score)
+    else:
+        from .engine import VectorGallery
+        store = VectorGallery(ctx, emb.shape[1], capacity=max(128, len(targets)))
+        try:
+            store.upsert(list(range(len(targets))), emb)
+            res = store.templates(dict(enumerate(names)), None, min_score)
+        finally:
+            store._gal.close()
+    out = []
+    for p, name in enumerate(res.persons):
+        if res.cohesion[p] > 0:
+            out.append((res.templates[p].astype(np.float32), name))
+        else:
+            logging.warning(f"No template for {name}: its faces cancel or were all dropped. Skipping...")
+    return out
+
+
 def gallery_from_targets(ctx: Context, targets: Sequence[Tuple[np.ndarray, str]]) -> Gallery:
     """The `targets` list as a device-resident Gallery (what frame_processor scans, main.py:136-142)."""
     assert len(targets) > 0, "no targets: every gallery image was skipped"

@@ -281,6 +281,48 @@ def score_distribution(embeddings, labels, bins: int = 512):
     return ScoreDistribution(list(range(n)), hist, imp_via, imp_score, gen_via, gen_score, summary)
 
 
+# ---- identity templates: one row per person from many embeddings (no reference analogue: its build_targets takes one photograph per name) ----
+def identity_templates(embeddings, labels, weights=None, min_score=None):
+    """fid_templates_host on numpy arrays, no device: embeddings [n, dim] (any scale; a zero row takes no part) are normalised in float64 and
+    rounded to fp16 as the gallery stores them (as score_distribution does); labels: the person of every row, a sequence of n hashables (None
+    = unlabelled) or a mapping row index -> person; weights: None (equal), or the quality in [0, 1] of every row as a sequence or a mapping
+    (engine.weight_codes has the mapping to 1 .. 255); min_score: None drops nothing.  The rule of fid_gallery_templates (include/faceid.h):
+    exact integer sums, the same bytes as the device.  -> engine.TemplateResult keyed by the row index."""
+    from .._lib import load
+    from ..engine import TEMPLATE_KEEP_ALL, TEMPLATE_MAX_ROWS, TemplateResult, label_codes, persons_of, weight_codes
+    x = np.asarray(embeddings, dtype=np.float64)
+    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"identity_templates needs embeddings [n, dim], not {x.shape}")
+    n, dim = x.shape
+    if n > TEMPLATE_MAX_ROWS:
+        raise ValueError(f"identity_templates: {n} rows exceed the {TEMPLATE_MAX_ROWS} of one call")
+    as_map = lambda v, what: v if v is None or hasattr(v, "get") else dict(enumerate(_same_len(v, n, what)))
+    labels, weights = as_map(labels, "labels"), as_map(weights, "weights")
+    ids = list(range(n))
+    codes = label_codes(ids, labels)
+    persons = persons_of(ids, labels, codes)
+    P = len(persons)
+    if P == 0:
+        return TemplateResult(ids, [], np.zeros((0, dim), np.float16), np.zeros(n, np.float32), np.full(n, -1, np.int32), np.zeros((0, 4), np.int32),
+                              np.zeros(0, np.float32), np.zeros(6, np.int64))
+    w = weight_codes(ids, weights)
+    nrm = np.sqrt((x * x).sum(1, keepdims=True))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        unit = np.ascontiguousarray(np.where(nrm > 0, x / np.where(nrm > 0, nrm, 1), 0).astype(np.float16))
+    tpl, score, kept = np.empty((P, dim), np.float16), np.empty(n, np.float32), np.empty(n, np.int32)
+    person, cohesion, summary = np.empty((P, 4), np.int32), np.empty(P, np.float32), np.empty(6, np.int64)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    check(load().fid_templates_host(p(unit), n, dim, None, p(codes), p(w), n, P, C.c_float(TEMPLATE_KEEP_ALL if min_score is None else float(min_score)),
+                                    p(tpl), p(score), p(kept), p(person), p(cohesion), p(summary)))
+    return TemplateResult(ids, persons, tpl, score, kept, person, cohesion, summary)
+
+
+def _same_len(v, n, what):
+    if len(v) != n:
+        raise ValueError(f"identity_templates: {len(v)} {what} for {n} rows")
+    return v
+
+
 # ---- drawing (reference utils/helpers.py:126-179): with OpenCV on the host, cv2's primitives; without it, the library's host rasteriser
 # (fid_draw_faces_host: the raster rules of include/faceid.h -- the same pixels fid_draw_faces writes on the device) ----
 def _cv2():
